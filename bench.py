@@ -14,8 +14,11 @@ are synthetic (seeded N(0,1) images), resident in HBM before the
 architecture.  Headline workload = BASELINE.json configs[1]: config/SemiReward/usb_cv/flexmatch/flexmatch_cifar100_200_0.yaml (per-GPU
 batch 8 labelled + 8 weak + 8 strong).
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  ``value`` is the median of ``--repeats`` timed regions of exactly
-``--steps`` steps, each bracketed by barrier + synchronize (all of them are listed in ``repeats``).  Besides ``roofline`` and
+Prints ONE JSON line on rank 0 (contract in the task statement).  Exactly ``--steps`` steps are timed, split into ``--repeats`` consecutive
+regions, each bracketed by barrier + synchronize (all of them are listed in ``repeats``); ``ms_per_step`` is their total time / ``--steps``
+and ``value`` the images per second of that.  ``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs; the inputs and the weights are seeded, and that last step runs from the seeded state of the leg, so that runs and builds
+compare array for array).  Besides ``roofline`` and
 ``cpu_baseline`` the line carries ``also``: short legs of the other workloads BASELINE.json's north_star names (ViT-S/16 on 224x224x3, a
 scaled per-GPU batch, the pre-start_timing regime K = 0: each with its own ms_per_step and dominant-kernel roofline; the usb_nlp BERT-base
 and usb_audio Wav2Vec2-base + FreeMatch steps of configs[3] / [4] under their own metric names).
@@ -38,6 +41,57 @@ NS = dict(algorithm="srflexmatch", num_classes=100, num_train_iter=204800, epoch
 MFMA_BF16_DENSE_PEAK_TFLOPS = 2500.0      # MI355X_MICROARCH.md: ~2.5 PF dense bf16 (the 5 PF headline is 2:1 sparse)
 HBM_PEAK_TBS = 8.0                        # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 measured with a float4 copy)
 START_IT = 30000                          # it >= 25601 -> sr_decay() == 8 (88 % of the reference run)
+DUMP_MAX_BYTES = 64 << 20                 # --dump-outputs: all arrays together
+DUMP_PARAM_SAMPLE = 1 << 21               # --dump-outputs: elements kept of a parameter block larger than this (seeded, sorted indices)
+
+
+def dump_outputs(alg, dirname):
+    """Writes what the step just run computed, as a caller of it receives it: train_step's out_dict (loss, features) and log_dict (the logged
+    scalars), and the parameters the optimizer step left in the model, rewarder and generator (float tensors of their state_dict in order,
+    flattened; a block larger than DUMP_PARAM_SAMPLE elements as a seeded sample).  Returns {name: [shape, what]} for the result line."""
+    import numpy as np
+    import torch
+    arrays, index = {}, {}
+
+    def put(name, t, what):             # tensors as float32, python / deferred scalars as float64
+        a = t.detach().float().cpu().numpy() if torch.is_tensor(t) else np.asarray(float(t), dtype=np.float64)
+        arrays[name] = a
+        index[name] = [list(a.shape), what]
+
+    def walk(prefix, d, what):
+        for k, v in d.items():
+            name = "%s%s" % (prefix, k.replace("/", "_"))
+            if isinstance(v, dict):
+                walk(name + "_", v, what)
+            elif v is not None:
+                put(name, v, what)
+    torch.cuda.synchronize()
+    walk("", alg.out_dict, "out_dict")
+    walk("log_", alg.log_dict, "log_dict")
+    for part in ("model", "rewarder", "generator"):
+        obj = getattr(alg, part, None)
+        if obj is None:
+            continue
+        flat = [v.detach().reshape(-1) for v in obj.state_dict().values() if torch.is_tensor(v) and v.is_floating_point()]
+        if not flat:
+            continue
+        flat = torch.cat([v.to(flat[0].device, torch.float32) for v in flat])
+        n = flat.numel()
+        if n > DUMP_PARAM_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_PARAM_SAMPLE, replace=False))
+            put(part + "_params", flat[torch.from_numpy(idx).to(flat.device)], "%d of %d elements (numpy default_rng(0).choice, sorted)" % (
+                DUMP_PARAM_SAMPLE, n))
+        else:
+            put(part + "_params", flat, "all %d elements" % n)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return index
+
+
 def _latest_traffic_json():
     """profiles/rNN_hbm_traffic.json of the latest round (PMC passes of this same command, tools/traffic.sh; static, labelled as such in the line)."""
     import glob
@@ -53,7 +107,9 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; value = their median")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="split the --steps timed steps into this many consecutive fenced regions (at most one per step) to see their spread; "
+                         "ms_per_step = the total time / --steps either way")
     ap.add_argument("--bu", type=int, default=8, help="per-GPU unlabeled batch (reference yaml: 8, uratio 1)")
     ap.add_argument("--bl", type=int, default=0, help="per-GPU labelled batch (default = --bu, uratio 1)")
     ap.add_argument("--regime", choices=["sr", "pre"], default="sr", help="sr: it > start_timing (K=8); pre: K=0")
@@ -81,6 +137,10 @@ def parse_args(argv=None):
     ap.add_argument("--extra-budget", type=float, default=900.0,
                     help="seconds the phases AFTER the headline (secondary legs, gradient-exchange legs, CPU baseline) may take before the line is "
                          "printed with what is complete")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed step computed (loss, features, logged scalars, the "
+                         "updated parameters; a seeded sample of a block past %d elements) as DIR/<name>.npy in float32 / float64, at most %d MB; "
+                         "that step runs from the leg's seeded state, in a timed region of its own" % (DUMP_PARAM_SAMPLE, DUMP_MAX_BYTES >> 20))
     return ap.parse_args(argv)
 
 
@@ -398,7 +458,13 @@ class Leg:
             dt = float(t)
         return dt
 
-    def run(self, steps, warmup, repeats, roofline=True):
+    def run(self, steps, warmup, repeats, roofline=True, dump=""):
+        """Set-up steps, ``warmup`` steps, then exactly ``steps`` timed steps in min(repeats, steps) consecutive fenced regions.  dump: a
+        directory for dump_outputs() of the last timed step, which then runs in a region of its own from the seeded state the leg was built
+        with (loaded before it, untimed): bf16 training amplifies the run-to-run noise of the backward's atomics within a few steps, so only a
+        step from a fixed state computes the same arrays in every run."""
+        import io
+
         import torch
         from semireward_amd import ops
         a, world = self.a, self.ctx["world"]
@@ -406,6 +472,9 @@ class Leg:
         # set-up, untimed like building the model: the start-up autotune of the step schedule (share of the inference rows on the second
         # stream, srflexmatch._DeferTuner) runs its candidates as real training steps; the W warm-up and the K timed steps follow it
         # (data parallel: the gradient exchange is selected first -- distributed.ExchangeTuner -- then the step schedule)
+        if dump:                                           # the seeded state, before any step (the project's checkpoint: resume is exact)
+            start_state = io.BytesIO()
+            torch.save(m.get_save_dict(), start_state)
         tune_steps = 0
         tuning = lambda: (not m.dp.settled) or bool(getattr(m, "_tuners", None)) or bool(getattr(m, "_untuned", None))   # noqa: E731
         while (getattr(m, "_tuners", None) is not None or not m.dp.settled) and (tune_steps == 0 or tuning()) and tune_steps < 96:
@@ -427,8 +496,24 @@ class Leg:
             self.step()
         m.dp.comm_events = [] if self.dp_on else None          # event pairs around the gradient all-reduce of every timed step
         syncs0 = m.dp.agreement_syncs
-        dts = [self.timed(steps) for _ in range(repeats)]
+        nreg = max(1, min(repeats, steps))
+        sizes = [steps // nreg + (1 if r < steps % nreg else 0) for r in range(nreg)]
+        if dump and sizes[-1] > 1:
+            sizes[-1] -= 1
+            sizes.append(1)
+        dts = []
+        for r, n in enumerate(sizes):
+            replay = self.graph
+            if dump and r == len(sizes) - 1:
+                start_state.seek(0)
+                m.load_model(start_state)                  # (resumes at the saved it + 1: no rewarder update, like 9 in 10 steps)
+                self.graph = None                          # (loading replaces buffers a captured graph reads: this step launches eagerly)
+            dts.append(self.timed(n))
+            self.graph = replay
         syncs_timed = m.dp.agreement_syncs - syncs0
+        dumped = None
+        if dump and self.ctx["rank"] == 0:
+            dumped = {"dir": dump, "it": m.it - 1, "arrays": dump_outputs(m, dump)}
         ar_ms = None
         if self.dp_on:
             torch.cuda.synchronize()
@@ -436,14 +521,15 @@ class Leg:
             m.dp.comm_events = None
             if ev:
                 ar_ms = sum(x.elapsed_time(y) for x, y in ev) / len(ev)
-        dt = sorted(dts)[len(dts) // 2]
+        dt = sum(dts)
+        per = [1e3 * d / n for d, n in zip(dts, sizes)]
         K = m.sr_decay() if self.regime == "sr" else 0
         bl, bu = self.bl, self.bu
         out = {"metric": self.metric, "value": world * bu * steps / dt, "unit": self.unit, "n_gpus": world, "steps": steps, "warmup": warmup,
                "ms_per_step": 1e3 * dt / steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
                "data": "synthetic",
-               "repeats": {"n": len(dts), "ms_per_step": [round(1e3 * d / steps, 4) for d in dts], "value_is": "median",
-                           "spread_pct": round(100.0 * (max(dts) - min(dts)) / dt, 2)},
+               "repeats": {"n": len(sizes), "steps": sizes, "ms_per_step": [round(x, 4) for x in per], "value_is": "total time of the timed steps / steps",
+                           "spread_pct": round(100.0 * (max(per) - min(per)) * steps / (1e3 * dt), 2)},
                # `config` is FLAT (scalars and strings only): the driver's BENCH_rNN.json keeps those and drops nested values
                "config": {"workload": self.workload, "algorithm": self.alg_name, "bl": bl, "bu_w": bu, "bu_s": 0 if self.net == "wrn" else bu,
                           "K_passes": K,
@@ -487,6 +573,8 @@ class Leg:
             out["config"]["grad_exchange"] = m.dp.exchange
             out["rank_agreement_syncs"] = {"during_tuning": syncs0 + (m.dp.exchange_report or {}).get("agreement_syncs", 0),
                                            "in_timed_regions": syncs_timed}
+        if dumped is not None:
+            out["dump"] = dumped
         if roofline:
             # roofline pass: the SAME steps again, in this process, with HIP events (on the launch stream) around every GEMM-class launch.
             # Kept out of the timed regions because 2 x 145 event records per step cost ~0.9 ms of host time.  Every rank runs the pass
@@ -602,7 +690,7 @@ def worker(a):
                 print("bench.py: %s" % ctx["backend_note"], file=sys.stderr)
 
     head = Leg(a, ctx, net=a.net, img=a.img, bu=a.bu, bl=a.bl, regime=a.regime, alg=a.alg, elide=a.elide_unread_rows)
-    out = head.run(a.steps, a.warmup, max(1, a.repeats), roofline=not a.no_roofline)
+    out = head.run(a.steps, a.warmup, max(1, a.repeats), roofline=not a.no_roofline, dump=a.dump_outputs)
     if rank == 0 and os.environ.get("SR_PHASES", "0") != "0":
         print("phases (ms since step start: gpu, host):", {k: (round(v[0], 2), round(v[1], 2)) for k, v in head.alg.phase_report().items()},
               file=sys.stderr)
@@ -647,7 +735,7 @@ def worker(a):
             leg = None
             try:
                 leg = Leg(a, ctx, **kw)
-                o = leg.run(nsteps, 2, 3, roofline=roof and not a.no_roofline)
+                o = leg.run(nsteps, 2, 1, roofline=roof and not a.no_roofline)
                 keep = {k: o[k] for k in ("metric", "value", "unit", "ms_per_step", "repeats", "n_gpus") if k in o}
                 keep.update(leg=tag, workload=o["config"]["workload"], K_passes=o["config"]["K_passes"],
                             per_gpu_batch={k: o["config"][k] for k in ("bl", "bu_w", "bu_s")})
@@ -696,7 +784,7 @@ def worker(a):
                 # of them spends ~30 tuning steps (each with a blocking rank agreement) before its timed region
                 leg.alg.defer_share = out["config"].get("deferred_share")
                 leg.graph_mode = "0"
-                o = leg.run(max(4, a.steps // 2), 2, 3, roofline=False)
+                o = leg.run(max(4, a.steps // 2), 2, 1, roofline=False)
                 ab[tag] = {"ms_per_step": o["ms_per_step"], "value": o["value"], "allreduce_ms_per_step": o.get("allreduce_ms_per_step"),
                            "note": {"allreduce": "one all-reduce of the flat fp32 block after the backward",
                                     "overlap": "allreduce_ms_per_step = what is left exposed behind the backward (event pair around all_reduce_grads)",
