@@ -235,6 +235,34 @@ int srhip_patch_assemble(const float* tok, const float* bp, const float* cls, co
                          void* stream);
 int srhip_patch_grad_operands(const float* dx, void* dx_tok_bf16, float* dpos, float* dcls, int B, int Np, int D, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Split-bf16 ("bf16x3") forward of the rows that decide the pseudo-label masks (read_rows_precision = bf16x3; csrc/precise.hip).
+ * Every fp32 operand x is split into hi = bf16_rne(x), lo = bf16_rne(x - hi); a product is hi.hi + hi.lo + lo.hi on the bf16 MFMA with fp32
+ * accumulation (lo.lo dropped): ~4e-6 relative error against fp64 where the bf16 operands of srhip_gemm_nt give ~2e-3.  Activations are fp32.
+ *
+ * srhip_gemm_nt_x3: C(f32)[M,N] = epilogue(A(f32)[M,K] . W(f32)[N,K]^T) -- the nn.Linear forwards of vit.py:93-98,105 (qkv, proj),
+ * :69-75 (fc1, fc2) and the patch-embedding conv as a GEMM (:39-44), W read straight from the fp32 parameter block.
+ *   SRHIP_X3_EPI_F32       : C = acc + bias
+ *   SRHIP_X3_EPI_GELU_F32  : C = gelu_erf(acc + bias)                                               (nn.GELU(), vit.py:63,72)
+ *   SRHIP_X3_EPI_RESID_F32 : C = C + row_scale[m / rows_per_sample] * (acc + bias), row_scale NULL = 1  (DropPath + residual, vit.py:164-165)
+ * bias may be NULL.  Requirements: K % 32 == 0, lda >= K and ldw >= K multiples of 4, ldc >= N, A and W 16-byte aligned; any M (ragged tails
+ * included) up to 65535 * 128 rows, any N.  row_scale only with SRHIP_X3_EPI_RESID_F32.
+ * srhip_attn_fwd_x3: head_dim 64, qkv fp32 [B*N, 3*H*64] as srhip_gemm_nt_x3 writes it, out fp32 [B*N, H*64]; QK^T and PV as bf16x3 products,
+ * softmax in fp32 (accurate expf; the row sum over the unrounded probabilities).  Replaces vit.py:100-104.  N <= 512, B <= 65535.
+ * srhip_layernorm_fwd_f32: srhip_layernorm_fwd with an fp32 output [M, D] (same statistics, same kernel body).
+ * srhip_patch_im2col_f32: srhip_patch_im2col with fp32 output (the A operand of srhip_gemm_nt_x3). */
+enum {
+  SRHIP_X3_EPI_F32 = 0,
+  SRHIP_X3_EPI_GELU_F32 = 1,
+  SRHIP_X3_EPI_RESID_F32 = 2
+};
+int srhip_gemm_nt_x3(int epilogue, const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
+                     const float* bias, const float* row_scale, int rows_per_sample, void* stream);
+int srhip_attn_fwd_x3(const float* qkv, float* out, int B, int N, int H, float scale, void* stream);
+int srhip_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float eps, float* out, float* mean, float* rstd, int M,
+                            int D, void* stream);
+int srhip_patch_im2col_f32(const float* img, const int* img_index, float* out, int B, int C, int HW, int ps, void* stream);
+
 /* Final norm on the cls token, global_pool='token', classifier head (vit.py:282, :296-305) (K7).
  * feat fp32 [B,D], logits fp32 [B,C]; xhat [B,D] / rstd [B] saved for the backward when non-NULL. */
 int srhip_cls_head_fwd(const float* x, const float* gamma, const float* beta, float eps, const float* Wh, const float* bh,

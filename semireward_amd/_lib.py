@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libsrhip.so")
 
 EPI_BF16, EPI_GELU_BF16, EPI_RESID_F32, EPI_DGELU_BF16, EPI_F32 = range(5)
+X3_EPI_F32, X3_EPI_GELU_F32, X3_EPI_RESID_F32 = range(3)     # srhip_gemm_nt_x3
 
 P, I, F, L, Dbl, U = c_void_p, c_int, c_float, c_long, c_double, c_uint
 SIGNATURES = {
@@ -49,6 +50,10 @@ SIGNATURES = {
     "srhip_patch_im2col": (I, [P, P, P, I, I, I, I, P]),
     "srhip_patch_assemble": (I, [P, P, P, P, P, I, I, I, P]),
     "srhip_patch_grad_operands": (I, [P, P, P, P, I, I, I, P]),
+    "srhip_gemm_nt_x3": (I, [I, P, I, P, I, P, I, I, I, I, P, P, I, P]),
+    "srhip_attn_fwd_x3": (I, [P, P, I, I, I, F, P]),
+    "srhip_layernorm_fwd_f32": (I, [P, P, P, F, P, P, P, I, I, P]),
+    "srhip_patch_im2col_f32": (I, [P, P, P, I, I, I, I, P]),
     "srhip_cls_head_fwd": (I, [P, P, P, F, P, P, P, P, P, P, I, I, I, I, P]),
     "srhip_cls_head_fwd_scatter": (I, [P, P, P, F, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "srhip_cls_head_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),

@@ -14,6 +14,7 @@ What is restructured for MI355X -- results are unchanged because ViT rows are in
   * softmax/argmax of all passes is one launch, the K rewarder scorings are one grouped launch, the FlexMatch
     state updates stay sequential (they are order dependent) but never leave the device.
 """
+import argparse
 import os
 
 import torch
@@ -100,10 +101,12 @@ class _Plan:
     """Row bookkeeping of one step: every column is one (pass, image) row of the batched forward; ``grad_cols`` are the
     rows whose logits enter the loss (they are run with activations kept), all other rows run in inference mode."""
 
-    def __init__(self, cols_img, grad_cols, device, skip_cols=(), read_cols=None, rows_per_col=None, defer_fraction=None):
+    def __init__(self, cols_img, grad_cols, device, skip_cols=(), read_cols=None, rows_per_col=None, defer_fraction=None, split_read=False):
         """read_cols: the inference columns whose logits / features the step actually READS (weak rows of every pass).  The others are
         computed because the reference computes them (the strong and labelled rows of the passes whose loss is thrown away) -- same
-        launches, but nothing waits for them: they run on the second stream behind the gradient rows (``rest``)."""
+        launches, but nothing waits for them: they run on the second stream behind the gradient rows (``rest``).
+        split_read (read_rows_precision = bf16x3): the read launch becomes two -- the columns that are read (``x3``) and the unread ones moved
+        into it below for tile balance (``mix``, bf16 as before) -- and the launch order (perm_cols) is gradient | x3 | mix | deferred."""
         gset = set(grad_cols) | set(skip_cols)
         inf_all = [c for c in range(len(cols_img)) if c not in gset]
         rset = set(inf_all) if read_cols is None else set(read_cols)
@@ -143,10 +146,17 @@ class _Plan:
         self.inf_img = t([cols_img[c] for c in inf_cols], torch.int32)
         self.rest_img = t([cols_img[c] for c in rest_cols], torch.int32)
         self.ncols = len(cols_img)
+        self.x3_cols = self.x3_img = self.mix_cols = self.mix_img = None
+        if split_read:
+            x3 = [c for c in inf_cols if c in rset]
+            mix = [c for c in inf_cols if c not in rset]
+            self.x3_cols, self.x3_img = t(x3, torch.int64), t([cols_img[c] for c in x3], torch.int32)
+            self.mix_cols, self.mix_img = t(mix, torch.int64), t([cols_img[c] for c in mix], torch.int32)
+            self.perm_cols = t(list(grad_cols) + x3 + mix + list(rest_cols), torch.int64)
 
     @classmethod
     def cat_passes(cls, nl, nu, K, device, extra_pass0_strong=False, lb_every_pass=True, defer_unread=False, rows_per_col=None,
-                   elide_unread=False, defer_fraction=None):
+                   elide_unread=False, defer_fraction=None, split_read=False):
         """use_cat layout of SRFlexMatch / SRFixMatch: every pass is cat(x_lb, x_ulb_w, x_ulb_s); gradients flow from the
         labelled rows of pass 0 and the strong rows of the last pass.  lb_every_pass=False (use_cat=False, the usb_nlp / usb_audio
         configs): data_generator forwards only x_ulb_s and x_ulb_w (srflexmatch.py:83-90), so the labelled columns of the passes
@@ -163,9 +173,43 @@ class _Plan:
             skip = sorted(set(skip) | {k * Bt + j for k in range(1, K + 1) for j in range(nl)} |
                           {k * Bt + j for k in range(1, K) for j in range(nl + nu, Bt)})
         read = [k * Bt + j for k in range(K + 1) for j in range(nl, nl + nu)] if defer_unread else None      # the weak rows
-        p = cls(cols_img, grad, device, skip, read, rows_per_col, defer_fraction)
+        p = cls(cols_img, grad, device, skip, read, rows_per_col, defer_fraction, split_read)
         p.P, p.Bt = K + 1, Bt
         return p
+
+
+READ_ROWS_PRECISIONS = ("bf16", "bf16x3")
+
+
+def backbone_class(net_builder):
+    """The engine class a backbone builder returns, without building it: a class as such, or the ModuleSurface subclass defined in the builder's
+    module (nets/vit.py: VisionTransformer, ...).  None when it cannot be told (a wrapped builder): the built model is checked then."""
+    import inspect
+    import sys
+    from ..nets.surface import ModuleSurface
+    if inspect.isclass(net_builder):
+        return net_builder
+    mod = sys.modules.get(getattr(net_builder, "__module__", None) or "")
+    found = [c for c in vars(mod).values() if inspect.isclass(c) and issubclass(c, ModuleSurface) and c.__module__ == mod.__name__] if mod else []
+    return found[0] if len(found) == 1 else None
+
+
+def read_rows_precision(args, net_cls=None):
+    """Numeric mode of the rows that decide masks, pseudo labels and rewards (the weak rows of every pass): ``args.read_rows_precision``, else
+    the environment variable SR_READ_ROWS_PRECISION, else "bf16".
+      bf16   : bf16 GEMM operands, fp32 accumulation -- the engine's one mode, bit for bit;
+      bf16x3 : split-bf16 products and fp32 activations (csrc/precise.hip), ~500x closer to the reference's fp32 forward.
+    Raises ValueError for another value, NotImplementedError for bf16x3 on a backbone without that forward (``precise_rows``)."""
+    v = getattr(args, "read_rows_precision", None)
+    if v is None:
+        v = os.environ.get("SR_READ_ROWS_PRECISION", "bf16")
+    v = str(v).strip().lower()
+    if v not in READ_ROWS_PRECISIONS:
+        raise ValueError("read_rows_precision must be one of %s, got %r" % (", ".join(READ_ROWS_PRECISIONS), v))
+    if v == "bf16x3" and net_cls is not None and not getattr(net_cls, "precise_rows", False):
+        raise NotImplementedError("read_rows_precision: bf16x3 is built for the ViT engine only; backbone %s has no split-bf16 forward"
+                                  % getattr(net_cls, "__name__", net_cls))
+    return v
 
 
 class SRConsistencyBase(AlgorithmBase):
@@ -173,7 +217,10 @@ class SRConsistencyBase(AlgorithmBase):
     differ only in their MaskingHook and in whether ``train_step`` receives ``idx_ulb``."""
 
     def __init__(self, args, net_builder, tb_log=None, logger=None):
+        # checked before any device work; a builder whose class cannot be told is checked on the built model below
+        self.read_rows_precision = read_rows_precision(args, backbone_class(net_builder))
         super().__init__(args, net_builder, tb_log, logger)
+        read_rows_precision(argparse.Namespace(read_rows_precision=self.read_rows_precision), type(self.model))
         self._init_thresholds(args)
         self.N_k = args.N_k
         # sr_ema != 0 selects EMARewarder in the reference (srflexmatch.py:49-50); its forward is identical and its EMA
@@ -258,20 +305,27 @@ class SRConsistencyBase(AlgorithmBase):
         side = self._side_stream if self.overlap_grad_rows else None
         dp_grad = sel(pl.grad_cols, 0)
         ni, nr = pl.inf_cols.numel(), pl.rest_cols.numel()
-        chunks = [(pl.inf_cols, pl.inf_img, ng_)] if ni else []
+        if getattr(pl, "x3_cols", None) is not None:
+            # read_rows_precision = bf16x3: the columns the step reads run the split-bf16 chain; the unread columns _Plan moved into the
+            # read launch keep the bf16 kernels the whole launch would have taken (kernels_as_images), in a launch of their own
+            nx = pl.x3_cols.numel()
+            chunks = ([(pl.x3_cols, pl.x3_img, ng_, dict(precision="bf16x3"))] if nx else []) + \
+                ([(pl.mix_cols, pl.mix_img, ng_ + nx, dict(buftag="m", kernels_as_images=ni))] if ni > nx else [])
+        else:
+            chunks = [(pl.inf_cols, pl.inf_img, ng_, {})] if ni else []
         if side is None and nr:
-            chunks.append((pl.rest_cols, pl.rest_img, ng_ + ni))
-        dps = [sel(cols, a) for cols, _, a in chunks]
+            chunks.append((pl.rest_cols, pl.rest_img, ng_ + ni, {}))
+        dps = [sel(cols, a) for cols, _, a, _ in chunks]
         dp_rest = sel(pl.rest_cols, ng_ + ni) if (side is not None and nr) else None
-        chunks = [(cols, imgi) for cols, imgi, _ in chunks]
+        chunks = [(cols, imgi, kw) for cols, imgi, _, kw in chunks]
         if side is not None:
             ready = torch.cuda.Event()
             ready.record(main)                       # parameters, images, DropPath draws are final here
-        for (cols, imgi), dpi in zip(chunks, dps):
+        for (cols, imgi, kw), dpi in zip(chunks, dps):
             if scatter:                  # the head writes the rows of the step's tables itself
-                m.forward_features(imgs, imgi, dpi, save=False, out=(logits, feats, cols))
+                m.forward_features(imgs, imgi, dpi, save=False, out=(logits, feats, cols), **kw)
             else:
-                lg, ft, _ = m.forward_features(imgs, imgi, dpi, save=False)
+                lg, ft, _ = m.forward_features(imgs, imgi, dpi, save=False, **kw)
                 logits.index_copy_(0, cols, lg)
                 feats.index_copy_(0, cols, ft)
         if side is not None:
@@ -390,7 +444,8 @@ class SRConsistencyBase(AlgorithmBase):
         return _Plan.cat_passes(nl, nu, K, self.device, extra_pass0_strong=self.fairness_rows and K > 0,
                                 lb_every_pass=bool(self.use_cat), defer_unread=self.defer_unread_rows,
                                 rows_per_col=getattr(self.model.cfg, "num_tokens", None),
-                                elide_unread=self.elide_unread_rows, defer_fraction=defer_fraction)
+                                elide_unread=self.elide_unread_rows, defer_fraction=defer_fraction,
+                                split_read=self.read_rows_precision == "bf16x3")
 
     def _forward_passes(self, imgs, nl, nu, K):
         key = (nl, nu, K, bool(self.use_cat), self.elide_unread_rows)

@@ -40,7 +40,8 @@ class SRPseudoLabel(SRConsistencyBase):
         if key not in self._plans:
             cols_img = list(range(nl + nu)) + [nl + j for _ in range(K) for j in range(nu)]   # imgs = cat(x_lb, x_ulb_w)
             last = (nl + nu) + (K - 1) * nu if K > 0 else nl
-            pl = _Plan(cols_img, list(range(nl)) + list(range(last, last + nu)), self.device)
+            pl = _Plan(cols_img, list(range(nl)) + list(range(last, last + nu)), self.device,
+                       split_read=self.read_rows_precision == "bf16x3")      # (no read list: every inference column is read)
             pl.weak = [slice(nl, nl + nu)] + [slice(nl + nu + k * nu, nl + nu + (k + 1) * nu) for k in range(K)]
             self._plans[key] = pl
         return self._plans[key]

@@ -19,9 +19,10 @@ namespace {
 // Two rows per wave, all loads of both rows (and the affine) requested before the first reduction: a wave that handles one row is a chain of
 // exposed round trips (row, then gamma / beta) and the launch is bounded by wave turnover.  Lane -> column map and reduction order per row
 // are unchanged (bit-identical results).
-template <int NV>
+// TOUT = float: the fp32-output instantiation of the bf16x3 rows (srhip_layernorm_fwd_f32), same statistics and affine.
+template <int NV, typename TOUT = bf16_t>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                    const float* __restrict__ beta, float eps, bf16_t* __restrict__ out,
+                                                    const float* __restrict__ beta, float eps, TOUT* __restrict__ out,
                                                     float* __restrict__ mean, float* __restrict__ rstd, int M) {
   constexpr int D = NV * 128, RW = 2;
   const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RW, lane = threadIdx.x & 63;
@@ -50,10 +51,17 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 #pragma unroll
     for (int i = 0; i < NV; ++i) { const float a = v[r][i].x - mu, c = v[r][i].y - mu; q += a * a + c * c; }
     const float rs = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
-    uint32_t* orow = reinterpret_cast<uint32_t*>(out + (size_t)row * D);
+    if constexpr (sizeof(TOUT) == 4) {
+      float2* orow = reinterpret_cast<float2*>(out + (size_t)row * D);
 #pragma unroll
-    for (int i = 0; i < NV; ++i)
-      orow[i * 64 + lane] = pack_bf2((v[r][i].x - mu) * rs * g[i].x + b[i].x, (v[r][i].y - mu) * rs * g[i].y + b[i].y);
+      for (int i = 0; i < NV; ++i)
+        orow[i * 64 + lane] = make_float2((v[r][i].x - mu) * rs * g[i].x + b[i].x, (v[r][i].y - mu) * rs * g[i].y + b[i].y);
+    } else {
+      uint32_t* orow = reinterpret_cast<uint32_t*>(out + (size_t)row * D);
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        orow[i * 64 + lane] = pack_bf2((v[r][i].x - mu) * rs * g[i].x + b[i].x, (v[r][i].y - mu) * rs * g[i].y + b[i].y);
+    }
     if (mean && lane == 0) { mean[row] = mu; rstd[row] = rs; }
   }
 }
@@ -545,17 +553,20 @@ __global__ void droppath_fill_kernel(float* __restrict__ out, const float* __res
 // Large-patch PatchEmbed (C * ps^2 > 64, e.g. ViT-S/16 at 224x224: K = 768): the conv with kernel = stride = ps is a GEMM of
 // the unfolded patches with the [D, C*ps*ps] filter (vit.py:39-44).  im2col -> srhip_gemm_nt -> assemble (+ bias, pos, cls).
 // out[b * Np + p][(c, i, j)] = img[idx[b]][c][py * ps + i][px * ps + j]  (bf16), (c, i, j) minor order == Conv2d weight.flatten(1)
+// TOUT = float: the fp32 operand of the bf16x3 patch-embedding product (srhip_patch_im2col_f32)
+template <typename TOUT = bf16_t>
 __global__ __launch_bounds__(256) void patch_im2col_kernel(const float* __restrict__ img, const int* __restrict__ img_index,
-                                                          bf16_t* __restrict__ out, int C, int HW, int ps) {
+                                                          TOUT* __restrict__ out, int C, int HW, int ps) {
   const int gw = HW / ps, Np = gw * gw, K = C * ps * ps;
   const int p = blockIdx.x, b = blockIdx.y, py = p / gw, px = p % gw;
   const int bi = img_index ? img_index[b] : b;
   const float* im = img + (size_t)bi * C * HW * HW;
-  bf16_t* o = out + ((size_t)b * Np + p) * K;
+  TOUT* o = out + ((size_t)b * Np + p) * K;
   for (int e = 2 * threadIdx.x; e < K; e += 512) {            // ps is even: the pair (j, j+1) stays inside one image row
     const int c = e / (ps * ps), i = (e / ps) % ps, j = e % ps;
     const float2 v = *reinterpret_cast<const float2*>(im + ((size_t)c * HW + py * ps + i) * HW + px * ps + j);
-    *reinterpret_cast<uint32_t*>(o + e) = pack_bf2(v.x, v.y);
+    if constexpr (sizeof(TOUT) == 4) *reinterpret_cast<float2*>(o + e) = v;
+    else *reinterpret_cast<uint32_t*>(o + e) = pack_bf2(v.x, v.y);
   }
 }
 
@@ -587,6 +598,19 @@ extern "C" int srhip_layernorm_fwd(const float* x, const float* gamma, const flo
   else if (D == 512) SR_LAUNCH(ln_fwd_kernel<4>, grid, block, 0, s, x, gamma, beta, eps, (bf16_t*)out, mean, rstd, M);
   else if (D == 384) SR_LAUNCH(ln_fwd_kernel<3>, grid, block, 0, s, x, gamma, beta, eps, (bf16_t*)out, mean, rstd, M);
   else SR_LAUNCH(ln_fwd_kernel<6>, grid, block, 0, s, x, gamma, beta, eps, (bf16_t*)out, mean, rstd, M);
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+
+extern "C" int srhip_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float eps, float* out,
+                                       float* mean, float* rstd, int M, int D, void* stream) {
+  if (!x || !out || M <= 0 || (D != 128 && D != 384 && D != 512 && D != 768) || ((mean == nullptr) != (rstd == nullptr))) return SR_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(cdiv(M, 8)), block(256);
+  if (D == 128) SR_LAUNCH((ln_fwd_kernel<1, float>), grid, block, 0, s, x, gamma, beta, eps, out, mean, rstd, M);
+  else if (D == 512) SR_LAUNCH((ln_fwd_kernel<4, float>), grid, block, 0, s, x, gamma, beta, eps, out, mean, rstd, M);
+  else if (D == 384) SR_LAUNCH((ln_fwd_kernel<3, float>), grid, block, 0, s, x, gamma, beta, eps, out, mean, rstd, M);
+  else SR_LAUNCH((ln_fwd_kernel<6, float>), grid, block, 0, s, x, gamma, beta, eps, out, mean, rstd, M);
   SR_CHECK_LAUNCH();
   return SR_OK;
 }
@@ -795,7 +819,15 @@ extern "C" int srhip_transpose_batched(const srhip_transpose_desc* desc_dev, int
 extern "C" int srhip_patch_im2col(const float* img, const int* img_index, void* out, int B, int C, int HW, int ps, void* stream) {
   if (!img || !out || B <= 0 || C <= 0 || ps <= 0 || (ps & 1) || HW % ps) return SR_EINVAL;
   const int gw = HW / ps;
-  SR_LAUNCH(patch_im2col_kernel, dim3(gw * gw, B), dim3(256), 0, (hipStream_t)stream, img, img_index, (bf16_t*)out, C, HW, ps);
+  SR_LAUNCH(patch_im2col_kernel<bf16_t>, dim3(gw * gw, B), dim3(256), 0, (hipStream_t)stream, img, img_index, (bf16_t*)out, C, HW, ps);
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+
+extern "C" int srhip_patch_im2col_f32(const float* img, const int* img_index, float* out, int B, int C, int HW, int ps, void* stream) {
+  if (!img || !out || B <= 0 || C <= 0 || ps <= 0 || (ps & 1) || HW % ps) return SR_EINVAL;
+  const int gw = HW / ps;
+  SR_LAUNCH(patch_im2col_kernel<float>, dim3(gw * gw, B), dim3(256), 0, (hipStream_t)stream, img, img_index, out, C, HW, ps);
   SR_CHECK_LAUNCH();
   return SR_OK;
 }

@@ -85,6 +85,7 @@ class VisionTransformer(ModuleSurface):
     rows_independent = True       # LayerNorm only: a row's outputs do not depend on which other rows share the launch
     scatter_outputs = True        # forward_features(out=...) writes logits / features at the caller's row numbers (no index_copy_)
     droppath_by_cols = True       # make_droppath(cols=...) lays the DropPath table out in the caller's column order (no index_select)
+    precise_rows = True           # forward_features(precision="bf16x3"): split-bf16 products, fp32 activations (read_rows_precision)
 
     def __init__(self, cfg=None, device="cuda", **kw):
         self.cfg = cfg if cfg is not None else VitConfig(**kw)
@@ -254,13 +255,22 @@ class VisionTransformer(ModuleSurface):
         return ctx
 
     # ---- forward ----------------------------------------------------------------------------------
-    def forward_features(self, img, img_index=None, droppath=None, save=False, B=None, buftag="", out=None):
+    def forward_features(self, img, img_index=None, droppath=None, save=False, B=None, buftag="", out=None, precision="bf16",
+                         kernels_as_images=None):
         """img fp32 [n_img, C, H, W]; img_index int32 [B] (optional gather); droppath fp32 [depth,2,B] or None.
-        Returns (logits [B,C], feat [B,D], ctx or None)."""
+        Returns (logits [B,C], feat [B,D], ctx or None).
+        precision="bf16x3" (rows without a backward only): the split-bf16 chain of _forward_x3 instead of the bf16-operand one.
+        kernels_as_images: pick the kernels a launch of that many images would take (rows split off a larger launch keep its results bit for bit)."""
+        if precision == "bf16x3":
+            assert not save, "the bf16x3 rows have no backward"
+            return self._forward_x3(img, img_index, droppath, B, buftag, out)
+        if precision != "bf16":
+            raise ValueError("precision must be 'bf16' or 'bf16x3', got %r" % (precision,))
         cfg = self.cfg
         D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
         B = int(img_index.numel()) if img_index is not None else (B or img.shape[0])
         M = B * N
+        Mk = max(M, (kernels_as_images or 0) * N)       # the launch size the kernel choice is made for
         f32, bf16 = torch.float32, torch.bfloat16
         tag = ("s" if save else "i") + buftag        # buftag: a second inference launch train on another stream needs its own workspaces
         ctx = None
@@ -274,7 +284,7 @@ class VisionTransformer(ModuleSurface):
             qkv = self._buf(tag + "qkv", (M, 3 * D), bf16)
             ao = self._buf(tag + "ao", (M, D), bf16)
         # rows without a backward run LN2 + fc1 + GELU + fc2 + residual as ONE kernel (ViT-S width; SRHIP_FUSED_MLP=0: off)
-        fused_mlp = (not save) and D == 384 and Hd % 128 == 0 and Hd <= 4096 and M >= _FUSED_MLP_MIN_ROWS and _FUSED_MLP
+        fused_mlp = (not save) and D == 384 and Hd % 128 == 0 and Hd <= 4096 and Mk >= _FUSED_MLP_MIN_ROWS and _FUSED_MLP
         hbuf = None if (fused_mlp or save) else self._buf(tag + "h", (M, Hd), bf16)
         fused_attn = (not save) and _FUSED_ATTN and ops.attn_block_supported(N, D, H)       # SRHIP_FUSED_ATTN=0: separate qkv GEMM + attention
         qkvx = self._buf(tag + "qkvx", (B, 3 * D), bf16) if (fused_attn and N == 257) else None
@@ -364,6 +374,58 @@ class VisionTransformer(ModuleSurface):
         ops.cls_head_fwd(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits,
                          ctx.xhat if save else None, ctx.rstd if save else None, B, N, D, C)
         return logits, feat, ctx
+
+    def _forward_x3(self, img, img_index, droppath, B, buftag, out):
+        """Inference rows in split-bf16 precision (read_rows_precision = bf16x3): every product is hi.hi + hi.lo + lo.hi of the bf16 planes of
+        its fp32 operands (csrc/precise.hip), activations stay fp32, LayerNorm / softmax / GELU / residual / head in fp32 in the order of
+        vit.py.  The weights are read from the fp32 parameter block.  Own workspaces (tag "p"): the bf16 chain's buffers are not touched."""
+        cfg = self.cfg
+        D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
+        B = int(img_index.numel()) if img_index is not None else (B or img.shape[0])
+        M = B * N
+        f32 = torch.float32
+        tag = "p" + buftag
+        x = self._buf(tag + "x", (M, D), f32)
+        ln = self._buf(tag + "ln", (M, D), f32)
+        ao = self._buf(tag + "ao", (M, D), f32)
+        wide = self._buf(tag + "wide", (M * max(3 * D, Hd),), f32)     # qkv [M, 3D], then the MLP hidden [M, Hd] of the same block
+        qkv, hbuf = wide[:M * 3 * D].view(M, 3 * D), wide[:M * Hd].view(M, Hd)
+        P = self.p
+        Kp = cfg.in_chans * cfg.patch_size ** 2
+        if Kp <= 64:                                # CIFAR-style patches: the direct kernel is fp32 already
+            ops.patch_embed_fwd(img, img_index, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("cls_token"),
+                                P("pos_embed"), x, B, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
+        else:                                       # ViT-S/16 at 224: fp32 unfold -> bf16x3 GEMM with the fp32 filter -> + bias / pos / cls
+            Np = N - 1
+            col = self._buf(tag + "col", (B * Np, Kp), f32)
+            tok = self._buf(tag + "tok", (B * Np, D), f32)
+            ops.patch_im2col_f32(img, img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
+            ops.gemm_nt_x3(ops.X3_EPI_F32, col, P("patch_embed.proj.weight"), tok, B * Np, D, Kp)
+            ops.patch_assemble(tok, P("patch_embed.proj.bias"), P("cls_token"), P("pos_embed"), x, B, Np, D)
+        scale = 64 ** -0.5
+        dst0, dst1 = (droppath.stride(0), droppath.stride(1)) if droppath is not None else (0, 0)
+        for i in range(cfg.depth):
+            b = "blocks.%d." % i
+            s1 = ops.RawRows(droppath, i * dst0) if droppath is not None else None
+            s2 = ops.RawRows(droppath, i * dst0 + dst1) if droppath is not None else None
+            ops.layernorm_fwd_f32(x, P(b + "norm1.weight"), P(b + "norm1.bias"), cfg.eps, ln, None, None, M, D)
+            ops.gemm_nt_x3(ops.X3_EPI_F32, ln, P(b + "attn.qkv.weight"), qkv, M, 3 * D, D, bias=P(b + "attn.qkv.bias"))
+            ops.attn_fwd_x3(qkv, ao, B, N, H, scale)
+            ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, ao, P(b + "attn.proj.weight"), x, M, D, D, bias=P(b + "attn.proj.bias"),
+                           row_scale=s1, rows_per_sample=N)
+            ops.layernorm_fwd_f32(x, P(b + "norm2.weight"), P(b + "norm2.bias"), cfg.eps, ln, None, None, M, D)
+            ops.gemm_nt_x3(ops.X3_EPI_GELU_F32, ln, P(b + "mlp.fc1.weight"), hbuf, M, Hd, D, bias=P(b + "mlp.fc1.bias"))
+            ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, hbuf, P(b + "mlp.fc2.weight"), x, M, D, Hd, bias=P(b + "mlp.fc2.bias"),
+                           row_scale=s2, rows_per_sample=N)
+        if out is not None:
+            logits_all, feats_all, rows = out
+            ops.cls_head_fwd_scatter(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), None, None, None, None,
+                                     feats_all, logits_all, rows, B, N, D, C)
+            return None, None, None
+        feat = torch.empty(B, D, dtype=f32, device=self.device)
+        logits = torch.empty(B, C, dtype=f32, device=self.device)
+        ops.cls_head_fwd(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, None, None, B, N, D, C)
+        return logits, feat, None
 
     def forward(self, x, only_fc=False, only_feat=False, **kw):
         """Reference-compatible entry (vit.py:285-306): returns {'logits','feat'}.  Inference-style call

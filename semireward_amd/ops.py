@@ -6,6 +6,7 @@ import torch
 
 from . import _lib
 from ._lib import EPI_BF16, EPI_DGELU_BF16, EPI_F32, EPI_GELU_BF16, EPI_RESID_F32  # noqa: F401
+from ._lib import X3_EPI_F32, X3_EPI_GELU_F32, X3_EPI_RESID_F32  # noqa: F401
 
 
 # Argument checks cost 0.3 us per pointer x ~4500 pointers per training step = 1.3 ms of host time, which is what bounds the step once the GPU
@@ -572,6 +573,34 @@ def patch_assemble(tok, bp, cls, pos, x, B, Np, D):
 
 def patch_grad_operands(dx, dx_tok, dpos, dcls, B, Np, D):
     _call("srhip_patch_grad_operands", _p(dx), _p(dx_tok), _p(dpos), _p(dcls), B, Np, D, _s())
+
+
+# ---- split-bf16 (bf16x3) forward of the rows that decide the masks (csrc/precise.hip) ---------------------------------------------------
+def gemm_nt_x3(epi, A, W, C, M, N, K, *, lda=None, ldw=None, ldc=None, bias=None, row_scale=None, rows_per_sample=0):
+    """C[M,N] = epilogue(A[M,K] . W[N,K]^T), fp32 operands as bf16 hi / lo planes, three MFMAs per fragment pair (see srhip_gemm_nt_x3)."""
+    args = (epi, _p(A), lda or K, _p(W), ldw or K, _p(C), ldc or N, M, N, K, _p(bias), _p(row_scale), rows_per_sample, _s())
+    if _PROFILE is not None:        # flops: the fp32-equivalent product (3x that on the MFMA); bytes: fp32 operands once + C (read too for RESID)
+        _PROFILE.timed("srhip_gemm_nt_x3", args, 2.0 * M * N * K, "gemm_nt_x3_kernel<%d>" % epi,
+                       4.0 * (M * K + N * K) + 4.0 * M * N * (2 if epi == X3_EPI_RESID_F32 else 1))
+        return
+    _call("srhip_gemm_nt_x3", *args)
+
+
+def attn_fwd_x3(qkv, out, B, N, H, scale):
+    """out fp32 [B*N, H*64] = softmax(Q K^T * scale) V from qkv fp32 [B*N, 3*H*64], both products bf16x3 (srhip_attn_fwd_x3)."""
+    if _PROFILE is not None:        # flops: QK^T (taken twice: max pass + exp pass) + PV as fp32-equivalent work; bytes: qkv in, out
+        _PROFILE.timed("srhip_attn_fwd_x3", (_p(qkv), _p(out), B, N, H, scale, _s()), 4.0 * B * H * N * N * 64, "attn_fwd_x3_kernel",
+                       4.0 * B * N * 4 * H * 64)
+        return
+    _call("srhip_attn_fwd_x3", _p(qkv), _p(out), B, N, H, scale, _s())
+
+
+def layernorm_fwd_f32(x, gamma, beta, eps, out, mean, rstd, M, D):
+    _call("srhip_layernorm_fwd_f32", _p(x), _p(gamma), _p(beta), eps, _p(out), _p(mean), _p(rstd), M, D, _s())
+
+
+def patch_im2col_f32(img, img_index, out, B, C, HW, ps):
+    _call("srhip_patch_im2col_f32", _p(img), _p(img_index), _p(out), B, C, HW, ps, _s())
 
 
 def cls_head_fwd_scatter(x, gamma, beta, eps, Wh, bh, feat, logits, xhat, rstd, feat_all, logits_all, out_rows, B, N, D, C):
