@@ -281,7 +281,7 @@ class SRConsistencyBase(AlgorithmBase):
             dp_all = droppath_cols.to(self.device)                                                   # [depth,2,ncols]
             sel = lambda cols, a: dp_all.index_select(2, cols).contiguous()                          # noqa: E731
         elif m.training and m.cfg.drop_path_rate > 0:
-            if getattr(m, "droppath_by_cols", False):
+            if m.droppath_by_cols:
                 # ONE launch: the columns of the draw in launch order; a launch train's table is the slice [a, a + len(cols))
                 dp_all = m.make_droppath(pl.ncols, cols=pl.perm_cols)
                 sel = lambda cols, a: dp_all[:, :, a:a + cols.numel()]                               # noqa: E731
@@ -291,7 +291,7 @@ class SRConsistencyBase(AlgorithmBase):
         else:
             dp_all = None
             sel = lambda cols, a: None                                                               # noqa: E731
-        scatter = getattr(m, "scatter_outputs", False)
+        scatter = m.scatter_outputs
         logits = torch.empty(pl.ncols, C, dtype=torch.float32, device=self.device)
         feats = torch.empty(pl.ncols, D, dtype=torch.float32, device=self.device)
         # The gradient-carrying rows (16 of 216 images at the reference batch) run on a SECOND HIP stream: their launches are
@@ -337,8 +337,7 @@ class SRConsistencyBase(AlgorithmBase):
                 if torch.is_tensor(t_) and not capturing:
                     t_.record_stream(side)
             with torch.cuda.stream(side), ops.stream_scope():
-                if hasattr(m, "ensure_transposed"):
-                    m.ensure_transposed()          # backward-only operands of the new parameters: here they delay nothing
+                m.ensure_transposed()              # backward-only operands of the new parameters: here they delay nothing
                 lg_g, ft_g, ctx = m.forward_features(imgs, pl.grad_img, dp_grad, save=True,
                                                      **(dict(out=(logits, feats, pl.grad_cols)) if scatter else {}))
                 grad_done = torch.cuda.Event()
@@ -453,7 +452,7 @@ class SRConsistencyBase(AlgorithmBase):
             self._untuned.discard(key)
             del self._plans[key]
         if key not in self._plans:
-            if self.elide_unread_rows and not getattr(self.model, "rows_independent", False):
+            if self.elide_unread_rows and not self.model.rows_independent:
                 raise ValueError("elide_unread_rows needs a backbone without batch statistics (ViT / BERT / Wav2Vec2 engines)")
             self._plans[key] = self._make_plan(nl, nu, K, defer_fraction=self.defer_share)
             if not self.dp.settled:
@@ -521,7 +520,7 @@ class SRConsistencyBase(AlgorithmBase):
 
     def _train_step(self, x_lb, y_lb, idx_ulb, x_ulb_w, x_ulb_s):
         it = self.it
-        if getattr(self.model, "takes_tokens", False):
+        if self.model.takes_tokens:
             # usb_nlp: x_* are {'input_ids','attention_mask'} dicts, each batch padded to its own longest row (nlp_collactor.py:63-69);
             # the reference forwards them in separate model calls (use_cat=False, :118-128) -- here they share the batched launches,
             # filled up to the longest of the three (TokenBatch.cat: identical results, see nets/bert.py)

@@ -54,7 +54,7 @@ class SRPseudoLabel(SRConsistencyBase):
         it = self.it
         K = self.sr_decay() if it > self.start_timing else 0                                        # :126, :62
         P, C = K + 1, self.num_classes
-        if getattr(self.model, "takes_tokens", False):       # usb_nlp: dict batches, padded separately (see SRConsistencyBase._train_step)
+        if self.model.takes_tokens:       # usb_nlp: dict batches, padded separately (see SRConsistencyBase._train_step)
             tb = [self._tokens(x) for x in (x_lb, x_ulb_w)]
             nl, nu = tb[0].S, tb[1].S
             imgs = self._token_cat(tb)
@@ -65,7 +65,7 @@ class SRPseudoLabel(SRConsistencyBase):
         dpc = None
         if self.inject_droppath is not None:        # tests: [ (dp_lb, dp_ulb), dp_ulb(pass 1), ... ]
             dpc = torch.cat([self.inject_droppath[0][0], self.inject_droppath[0][1]] + list(self.inject_droppath[1:P]), dim=2)
-        bn_backbone = getattr(self.model, "couples_batch_rows", False)
+        bn_backbone = self.model.couples_batch_rows
         if bn_backbone:
             # BatchNorm backbone (classic_cv, WRN): every model call of the reference is its own statistics group, so the calls stay
             # separate launches -- model(x_lb) moves the running statistics (:96), every model(x_ulb_w) runs under Bn_Controller.freeze_bn

@@ -103,7 +103,7 @@ class AlgorithmBase:
         self.dataset_dict = self.set_dataset()
         self.loader_dict = self.set_data_loader()
         self.model = self.set_model()
-        if getattr(self.model, "couples_batch_rows", False):
+        if self.model.couples_batch_rows:
             self.model.dp = self.dp          # BatchNorm backbone under data parallel = SyncBatchNorm, as the reference's send_model_cuda (misc.py:55)
         self.ema_model = self.set_ema_model()
         self.optimizer, self.scheduler = self.set_optimizer()
@@ -173,8 +173,7 @@ class AlgorithmBase:
             return self.model        # ema_m == 0 -> shadow == params after every step (misc.py:152-155): alias, 0 bytes moved
         ema = self.net_builder(num_classes=self.num_classes, device=self.device)
         ema.load_state_dict(self.model.state_dict())
-        if hasattr(ema, "buffers"):          # BatchNorm statistics are not averaged: EMAHook copies the model's (core/hooks/ema.py:20-24)
-            ema.buffers = self.model.buffers
+        ema.buffers = self.model.buffers     # BatchNorm statistics are not averaged: EMAHook copies the model's (core/hooks/ema.py:20-24)
         return ema
 
     def set_optimizer(self):

@@ -112,7 +112,6 @@ class TokenBatch:
 
 
 class ClassificationBert(PostLNEncoderMixin):
-    couples_batch_rows = False
     takes_tokens = True
     rows_independent = True       # LayerNorm only, counter-based dropout indexed per row
 
@@ -121,41 +120,11 @@ class ClassificationBert(PostLNEncoderMixin):
         cfg = self.cfg
         self.device = torch.device(device)
         self.num_features = cfg.hidden
-        self.names_shapes = param_names_shapes(cfg)
-        self.offsets, o = {}, 0
-        for n, s in self.names_shapes:
-            self.offsets[n] = (o, s)
-            o += int(torch.Size(s).numel())
-            o = (o + 7) // 8 * 8                     # 16-byte alignment of every tensor in the bf16 copy
-        self.numel = o
-        f32, bf16 = torch.float32, torch.bfloat16
-        self.flat = torch.zeros(o, dtype=f32, device=self.device)
-        self.grad = torch.zeros(o, dtype=f32, device=self.device)
-        self.flat_bf16 = torch.zeros(o, dtype=bf16, device=self.device)
+        self._init_block(param_names_shapes(cfg), align=8, bf16=True)     # 16-byte alignment of every tensor in the bf16 copy
         self.enc_alloc_wT()                           # per layer: transposed bf16 operands of the dX products
         self.enc_p = dict(attn=cfg.p_drop, hidden=cfg.p_drop, act=0.0)
-        self.training = True
-        self._ws, self._wT_desc = {}, None
         self._rng_calls, self.seed = 0, 0
         self.inject_seed = None                       # tests: the 64-bit dropout seed of the next forward calls
-
-    # ---- parameter plumbing (same surface as nets/vit.py) --------------------------------------------
-    def p(self, name, buf=None):
-        """Flat view of parameter ``name`` inside ``buf`` (default: the parameter block).  Cached per (name, buffer): building a slice view costs
-        ~3 us of host time and a step asks for ~500 of them -- more than half of the step's enqueue time before the cache."""
-        b = self.flat if buf is None else buf
-        if not (b is self.flat or b is self.grad or b is getattr(self, "flat_bf16", None)):
-            o, s = self.offsets[name]                     # some other block (optimizer state, a test's copy): no entry is kept for it
-            return b[o:o + int(torch.Size(s).numel())]
-        pv = self.__dict__.setdefault("_pviews", {})
-        ent = pv.get((name, id(b)))
-        if ent is None:
-            o, s = self.offsets[name]
-            ent = pv[(name, id(b))] = (b, b[o:o + int(torch.Size(s).numel())])     # (holds ``b``: its id stays unique)
-        return ent[1]
-
-    def view(self, name, buf=None):
-        return self.p(name, buf).view(self.offsets[name][1])
 
     def enc_names(self, i):
         p = _layer(i)
@@ -165,23 +134,6 @@ class ClassificationBert(PostLNEncoderMixin):
                     w1=p + "intermediate.dense.weight", b1=p + "intermediate.dense.bias",
                     w2=p + "output.dense.weight", b2=p + "output.dense.bias",
                     ln2_w=p + "output.LayerNorm.weight", ln2_b=p + "output.LayerNorm.bias")
-
-    def named_parameters(self):
-        return [(n, self.view(n)) for n, _ in self.names_shapes]
-
-    def named_grads(self):
-        return [(n, self.view(n, self.grad)) for n, _ in self.names_shapes]
-
-    def state_dict(self):
-        return {n: self.view(n).detach().clone() for n, _ in self.names_shapes}
-
-    def load_state_dict(self, sd, strict=True):
-        for n, s in self.names_shapes:
-            if n in sd:
-                self.view(n).copy_(torch.as_tensor(sd[n]).to(self.device, torch.float32).reshape(s))
-            elif strict:
-                raise KeyError(n)
-        self.refresh_operands()
 
     def init_weights(self, seed=0):
         """HF BertPreTrainedModel._init_weights: normal(0, 0.02) for Linear / Embedding weights ([PAD] row zero), LayerNorm 1 / 0, biases 0;
@@ -200,18 +152,6 @@ class ClassificationBert(PostLNEncoderMixin):
                 sd[n] = torch.randn(s, generator=g) * 0.02
         sd[E + "word_embeddings.weight"][self.cfg.pad_id].zero_()
         self.load_state_dict(sd)
-
-    def refresh_operands(self):
-        ops.cast_f32_bf16(self.flat, self.flat_bf16, self.numel)
-        self.refresh_transposed()
-
-    def refresh_transposed(self):
-        if self._wT_desc is None:
-            self._wT_desc = ops.make_transpose_desc(self.enc_transpose_items(), self.device)
-        ops.transpose_batched(*self._wT_desc)
-
-    def no_weight_decay(self):
-        return []
 
     frozen_params = ("bert.pooler.dense.weight", "bert.pooler.dense.bias")    # feed nothing on this path: grad None in the reference
 
@@ -232,23 +172,6 @@ class ClassificationBert(PostLNEncoderMixin):
     def group_matcher(self, coarse=False, prefix=""):
         return dict(stem=r"^{}bert.embeddings".format(prefix), blocks=r"^{}bert.encoder.layer.(\d+)".format(prefix))
 
-    def train(self, mode=True):
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def zero_grad(self):
-        self.grad.zero_()
-
-    def _buf(self, key, shape, dtype):
-        t = self._ws.get(key)
-        if t is None or t.shape != torch.Size(shape) or t.dtype != dtype:
-            t = torch.empty(shape, dtype=dtype, device=self.device)
-            self._ws[key] = t
-        return t
-
     def next_seed(self):
         """64-bit dropout seed of one forward call (None in eval mode / p_drop == 0)."""
         if not self.training or self.cfg.p_drop <= 0.0:
@@ -261,13 +184,13 @@ class ClassificationBert(PostLNEncoderMixin):
     # ---- forward ----------------------------------------------------------------------------------------
     def _ctx_buffers(self, B, L, tag):
         key = ("ctx", B, L, tag)
-        if key in self._ws:
-            return self._ws[key]
+        if key in self._buf_cache:
+            return self._buf_cache[key]
         c = types.SimpleNamespace()
         self.enc_alloc_ctx(c, B, L)
         self.head_alloc_ctx(c, B)
         c.st0 = torch.empty(2, B * L, dtype=torch.float32, device=self.device)
-        self._ws[key] = c
+        self._buf_cache[key] = c
         return c
 
     def forward_features(self, tok, seq_index=None, droppath=None, save=False, B=None, seed="auto", tag="", buftag=""):

@@ -11,8 +11,8 @@ arithmetic up to parameter names, LayerNorm eps and one extra dropout after the 
     x    = LayerNorm(y2)                             srhip_postln_fwd
 
 and a hand-written backward (post-LN: the gradient of a LayerNorm input feeds the residual path in fp32 and, dropout-masked, the branch's
-dX / dW products in bf16).  A host class mixes this in and provides: ``cfg`` (hidden, inter, heads, layers, eps), ``p`` / ``view`` /
-``flat_bf16`` / ``grad`` / ``offsets``, ``enc_names(i)`` (parameter names of layer i) and ``enc_p`` (dropout probabilities).
+dX / dW products in bf16).  A host class derives from this and provides: ``cfg`` (hidden, inter, heads, layers, eps), the flat block
+(``ModuleSurface._init_block``), ``enc_names(i)`` (parameter names of layer i) and ``enc_p`` (dropout probabilities).
 LayerDrop (Wav2Vec2, train mode): ``skip[i]`` leaves layer i out of forward and backward.
 """
 import torch
@@ -40,7 +40,7 @@ class PostLNEncoderMixin(ModuleSurface):
                         w1=torch.zeros(D, I, dtype=bf16, device=self.device), w2=torch.zeros(I, D, dtype=bf16, device=self.device))
                    for _ in range(self.cfg.layers)]
 
-    def enc_transpose_items(self):
+    def transpose_items(self):
         items, D, I = [], self.cfg.hidden, self.cfg.inter
         for i in range(self.cfg.layers):
             nm, t = self.enc_names(i), self.wT[i]
@@ -131,8 +131,8 @@ class PostLNEncoderMixin(ModuleSurface):
         per layer (BERT: 113 MB x 12 of 288 GB) they feed ONE launch behind the layer loop: 1 296 tiles in a persistent walk
         (srhip_gemm_tn_grouped_pp_f32: 113 us per layer, tools/gemm_tn_pp_bench.py)."""
         key = ("encbwd", M, id(ctx))
-        if key in self._ws:
-            return self._ws[key]
+        if key in self._buf_cache:
+            return self._buf_cache[key]
         cfg = self.cfg
         D, I = cfg.hidden, cfg.inter
         mk = lambda c: [torch.empty(M, c, dtype=torch.bfloat16, device=self.device) for _ in range(cfg.layers)]   # noqa: E731
@@ -148,7 +148,7 @@ class PostLNEncoderMixin(ModuleSurface):
         T["ln_part"] = torch.zeros(2 * cfg.layers, LN_REP, 2, D, dtype=torch.float32, device=self.device)
         T["ln_desc"] = ops.make_ln_reduce_desc([(G(self.enc_names(i)[k + "_w"]), G(self.enc_names(i)[k + "_b"]))
                                                 for i in range(cfg.layers) for k in ("ln1", "ln2")], self.device)
-        self._ws[key] = T
+        self._buf_cache[key] = T
         return T
 
     def enc_dw_table(self, T, skip):

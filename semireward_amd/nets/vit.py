@@ -70,10 +70,6 @@ _FUSED_NEXT_LN = True      # ... which then also writes the next block's norm1 o
 _FUSED_MLP_MIN_ROWS = 16384
 
 
-def _round_up(a, b):
-    return (a + b - 1) // b * b
-
-
 class FwdContext:
     """Activations kept by a ``save=True`` forward for the hand-written backward."""
     __slots__ = ("B", "img", "img_index", "dp", "xs", "xmid", "ln1", "ln2", "qkv", "ao", "lse", "pre", "h", "st1", "st2",
@@ -86,71 +82,23 @@ class VisionTransformer(ModuleSurface):
     scatter_outputs = True        # forward_features(out=...) writes logits / features at the caller's row numbers (no index_copy_)
     droppath_by_cols = True       # make_droppath(cols=...) lays the DropPath table out in the caller's column order (no index_select)
     precise_rows = True           # forward_features(precision="bf16x3"): split-bf16 products, fp32 activations (read_rows_precision)
+    lazy_transposed = True        # the optimizer only marks the transposed weight copies stale (ensure_transposed)
 
     def __init__(self, cfg=None, device="cuda", **kw):
         self.cfg = cfg if cfg is not None else VitConfig(**kw)
         cfg = self.cfg
         self.device = torch.device(device)
-        self.names_shapes = param_names_shapes(cfg)
+        self._init_block(param_names_shapes(cfg), align=1, bf16=True)
         self.grad_ready_cb = None          # callable(lo, hi) or None: see backward() / distributed.DataParallel.install_overlap
-        self.offsets, o = {}, 0
-        for n, s in self.names_shapes:
-            self.offsets[n] = (o, s)
-            o += int(torch.Size(s).numel())
-        # 2-D GEMM weights must start on a 16-byte boundary in the bf16 copy (8 elements)
-        assert all(v[0] % 8 == 0 for k, v in self.offsets.items() if len(v[1]) == 2)
-        self.numel = o
-        self.flat = torch.zeros(o, dtype=torch.float32, device=self.device)
-        self.grad = torch.zeros(o, dtype=torch.float32, device=self.device)
-        self.flat_bf16 = torch.zeros(o, dtype=torch.bfloat16, device=self.device)
         self.wT = {}
-        self._wT_stale = True
         for i in range(cfg.depth):
             for w in self.GEMM_WEIGHTS:
                 n = "blocks.%d.%s" % (i, w)
                 r, c = self.offsets[n][1]
                 self.wT[n] = torch.zeros(c, r, dtype=torch.bfloat16, device=self.device)
         self.dp_probs = torch.linspace(0, cfg.drop_path_rate, cfg.depth).to(self.device)    # vit.py:247-249
-        self.training = True
-        self._ws = {}
-        self._wT_desc = None
         self._rng_calls = 0
         self.seed = 0
-
-    # ---- parameter plumbing ---------------------------------------------------------------------
-    def p(self, name, buf=None):
-        """Flat view of parameter ``name`` inside ``buf`` (default: the parameter block).  Cached per (name, buffer): building a slice view costs
-        ~3 us of host time and a step asks for ~500 of them -- more than half of the step's enqueue time before the cache."""
-        b = self.flat if buf is None else buf
-        if not (b is self.flat or b is self.grad or b is getattr(self, "flat_bf16", None)):
-            o, s = self.offsets[name]                     # some other block (optimizer state, a test's copy): no entry is kept for it
-            return b[o:o + int(torch.Size(s).numel())]
-        pv = self.__dict__.setdefault("_pviews", {})
-        ent = pv.get((name, id(b)))
-        if ent is None:
-            o, s = self.offsets[name]
-            ent = pv[(name, id(b))] = (b, b[o:o + int(torch.Size(s).numel())])     # (holds ``b``: its id stays unique)
-        return ent[1]
-
-    def view(self, name, buf=None):
-        return self.p(name, buf).view(self.offsets[name][1])
-
-    def named_parameters(self):
-        return [(n, self.view(n)) for n, _ in self.names_shapes]
-
-    def named_grads(self):
-        return [(n, self.view(n, self.grad)) for n, _ in self.names_shapes]
-
-    def state_dict(self):
-        return {n: self.view(n).detach().clone() for n, _ in self.names_shapes}
-
-    def load_state_dict(self, sd, strict=True):
-        for n, s in self.names_shapes:
-            if n in sd:
-                self.view(n).copy_(torch.as_tensor(sd[n]).to(self.device, torch.float32).reshape(s))
-            elif strict:
-                raise KeyError(n)
-        self.refresh_operands()
 
     def init_weights(self, seed=0):
         """The reference VisionTransformer has no init function: torch defaults -- nn.Linear / Conv2d kaiming_uniform(a = sqrt 5) =
@@ -169,51 +117,16 @@ class VisionTransformer(ModuleSurface):
                 sd[n] = (torch.rand(s_, generator=g) * 2 - 1) * bound
         self.load_state_dict(sd)
 
-    def refresh_operands(self):
-        """bf16 operand copy of the whole block + transposed GEMM weights (after any parameter change)."""
-        ops.cast_f32_bf16(self.flat, self.flat_bf16, self.numel)
-        self.refresh_transposed()
-
-    lazy_transposed = True   # the optimizer only marks the transposed weight copies stale (ensure_transposed)
-
-    def ensure_transposed(self):
-        """The transposed bf16 weight copies are operands of the BACKWARD only (dX products).  After an optimizer step they are refreshed
-        where it costs nothing -- the step's second stream, before the gradient rows' forward (srflexmatch._forward_plan) -- instead of at
-        the end of the optimizer step, on the critical path (40 us per step); backward() calls this again as the safety net."""
-        if self._wT_stale:
-            self.refresh_transposed()
-
-    def refresh_transposed(self):
-        """W [out,in] fp32 -> W^T [in,out] bf16 for all 4*depth GEMM weights: one batched launch."""
-        self._wT_stale = False
-        if self._wT_desc is None:
-            items = []
-            for n, t in self.wT.items():
-                r, c = self.offsets[n][1]
-                items.append((self.p(n), True, c, t, r, r, r, c, False))
-            self._wT_desc = ops.make_transpose_desc(items, self.device)
-        ops.transpose_batched(*self._wT_desc)
+    def transpose_items(self):
+        """W [out,in] fp32 -> W^T [in,out] bf16 for all 4*depth GEMM weights (the dX operands of the backward)."""
+        items = []
+        for n, t in self.wT.items():
+            r, c = self.offsets[n][1]
+            items.append((self.p(n), True, c, t, r, r, r, c, False))
+        return items
 
     def no_weight_decay(self):
         return {"pos_embed", "cls_token"}
-
-    def train(self, mode=True):
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def zero_grad(self):
-        self.grad.zero_()
-
-    # ---- workspaces -------------------------------------------------------------------------------
-    def _buf(self, key, shape, dtype):
-        t = self._ws.get(key)
-        if t is None or t.shape != torch.Size(shape) or t.dtype != dtype:
-            t = torch.empty(shape, dtype=dtype, device=self.device)
-            self._ws[key] = t
-        return t
 
     def make_droppath(self, B, cols=None):
         """timm DropPath scales [depth, 2, B] for one forward (vit.py:148,161); cols (int64 device tensor): only those columns of the draw, in
@@ -234,8 +147,8 @@ class VisionTransformer(ModuleSurface):
         """Activation buffers of a save=True forward.  Persistent per batch size (one live context per size), so the
         batched-transpose / grouped-GEMM descriptor tables that point into them are built once."""
         key = ("ctx", B)
-        if key in self._ws:
-            return self._ws[key]
+        if key in self._buf_cache:
+            return self._buf_cache[key]
         cfg = self.cfg
         D, N, H, Hd = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden
         M = B * N
@@ -251,7 +164,7 @@ class VisionTransformer(ModuleSurface):
         ctx.st2 = [(t[0], t[1]) for t in mk((2, M), f32)]
         ctx.xhat = torch.empty(B, D, dtype=f32, device=self.device)
         ctx.rstd = torch.empty(B, dtype=f32, device=self.device)
-        self._ws[key] = ctx
+        self._buf_cache[key] = ctx
         return ctx
 
     # ---- forward ----------------------------------------------------------------------------------
@@ -444,8 +357,8 @@ class VisionTransformer(ModuleSurface):
         Operands stay row-major [tokens, features]: srhip_gemm_tn_grouped_f32 gathers the MFMA fragments with LDS transpose
         reads, and sums the bias gradients on the way (no transposes, no column-sum kernels)."""
         key = ("bwdplan", M, id(ctx))
-        if key in self._ws:
-            return self._ws[key]
+        if key in self._buf_cache:
+            return self._buf_cache[key]
         cfg = self.cfg
         D, Hd = cfg.embed_dim, cfg.hidden
         mk = lambda c: torch.empty(M, c, dtype=torch.bfloat16, device=self.device)   # noqa: E731
@@ -480,7 +393,7 @@ class VisionTransformer(ModuleSurface):
                                ln_desc=ops.make_ln_reduce_desc([(G("blocks.%d.norm%d.weight" % (i, j)), G("blocks.%d.norm%d.bias" % (i, j)))
                                                                 for i in range(lo_l, hi_l) for j in (1, 2)], self.device)))
         out["groups"] = groups
-        self._ws[key] = out
+        self._buf_cache[key] = out
         return out
 
     def backward(self, ctx, dlogits):
@@ -491,7 +404,7 @@ class VisionTransformer(ModuleSurface):
     def _bwd_views(self, ctx, T, b0, b1):
         """Per-layer operands of the dX chain restricted to the images [b0, b1) (built once per range: a view costs ~3 us of host time)."""
         key = ("bwdviews", id(ctx), b0, b1)
-        v = self._ws.get(key)
+        v = self._buf_cache.get(key)
         if v is not None:
             return v
         cfg = self.cfg
@@ -513,7 +426,7 @@ class VisionTransformer(ModuleSurface):
                 g2=r(Ti["g2"]), dpre=r(Ti["dpre"]), g1=r(Ti["g1"]), dqkv=r(Ti["dqkv"]), pre=r(ctx.pre[i]), xmid=r(ctx.xmid[i]), xs=r(ctx.xs[i]),
                 st1=(r(ctx.st1[i][0]), r(ctx.st1[i][1])), st2=(r(ctx.st2[i][0]), r(ctx.st2[i][1])), qkv=r(ctx.qkv[i]), ao=r(ctx.ao[i]),
                 lse=im(ctx.lse[i])))
-        self._ws[key] = v
+        self._buf_cache[key] = v
         return v
 
     def backward_rows(self, ctx, dlogits, b0, b1):
@@ -596,13 +509,13 @@ class VisionTransformer(ModuleSurface):
         else:                                       # dWp += dx_tok^T col, dbp += colsum dx_tok (TN grouped GEMM, one problem); dpos, dcls
             Np = N - 1
             key = ("pebwd", B)
-            if key not in self._ws:
+            if key not in self._buf_cache:
                 col = torch.empty(B * Np, Kp, dtype=bf16, device=self.device)
                 dxt = torch.empty(B * Np, D, dtype=bf16, device=self.device)
                 gw = self.view("patch_embed.proj.weight", self.grad).view(D, Kp)
                 desc = ops.make_group_tn_desc([(dxt, col, gw, self.view("patch_embed.proj.bias", self.grad), D, Kp, B * Np)], self.device)
-                self._ws[key] = (col, dxt, desc)
-            col, dxt, desc = self._ws[key]
+                self._buf_cache[key] = (col, dxt, desc)
+            col, dxt, desc = self._buf_cache[key]
             ops.patch_im2col(ctx.img, ctx.img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
             ops.patch_grad_operands(dx, dxt, G("pos_embed"), G("cls_token"), B, Np, D)
             ops.gemm_tn_grouped_f32(desc[0], desc[1], desc[2], alpha=1.0, beta=1.0, flops=desc[3], nbytes=desc[4])

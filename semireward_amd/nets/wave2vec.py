@@ -114,23 +114,13 @@ def spec_augment_mask(rng, B, T, mask_prob, mask_length, min_masks):
 
 
 class ClassificationWave2Vec(PostLNEncoderMixin):
-    couples_batch_rows = False
-
     def __init__(self, cfg=None, device="cuda", **kw):
         self.cfg = cfg if cfg is not None else W2vConfig(**kw)
         cfg = self.cfg
         self.device = torch.device(device)
         self.num_features = cfg.hidden
-        self.names_shapes = param_names_shapes(cfg)
-        self.offsets, o = {}, 0
-        for n, s in self.names_shapes:
-            self.offsets[n] = (o, s)
-            o = (o + int(torch.Size(s).numel()) + 7) // 8 * 8
-        self.numel = o
+        self._init_block(param_names_shapes(cfg), align=8, bf16=True)
         f32, bf16, dev = torch.float32, torch.bfloat16, self.device
-        self.flat = torch.zeros(o, dtype=f32, device=dev)
-        self.grad = torch.zeros(o, dtype=f32, device=dev)
-        self.flat_bf16 = torch.zeros(o, dtype=bf16, device=dev)
         self.enc_alloc_wT()
         self.enc_p = dict(attn=cfg.p_attn, hidden=cfg.p_hidden, act=cfg.p_act)
         C, D, k, G = cfg.conv_dim[0], cfg.hidden, cfg.pos_k, cfg.pos_groups
@@ -141,28 +131,8 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
         self.pos_norms = torch.zeros(k, dtype=f32, device=dev)
         self.pos_Wf = torch.zeros(G, self.cg, k * self.cg, dtype=bf16, device=dev)
         self.pos_Wb = torch.zeros(G, self.cg, k * self.cg, dtype=bf16, device=dev)
-        self.training = True
-        self._ws, self._wT_desc = {}, None
         self._rng_calls, self.seed = 0, 0
         self.inject = None            # tests: dict(seed=..., spec_mask=bool [B, T], skip=[...]) used by the next forward calls
-
-    # ---- parameter plumbing ---------------------------------------------------------------------------------
-    def p(self, name, buf=None):
-        """Flat view of parameter ``name`` inside ``buf`` (default: the parameter block).  Cached per (name, buffer): building a slice view costs
-        ~3 us of host time and a step asks for ~500 of them -- more than half of the step's enqueue time before the cache."""
-        b = self.flat if buf is None else buf
-        if not (b is self.flat or b is self.grad or b is getattr(self, "flat_bf16", None)):
-            o, s = self.offsets[name]                     # some other block (optimizer state, a test's copy): no entry is kept for it
-            return b[o:o + int(torch.Size(s).numel())]
-        pv = self.__dict__.setdefault("_pviews", {})
-        ent = pv.get((name, id(b)))
-        if ent is None:
-            o, s = self.offsets[name]
-            ent = pv[(name, id(b))] = (b, b[o:o + int(torch.Size(s).numel())])     # (holds ``b``: its id stays unique)
-        return ent[1]
-
-    def view(self, name, buf=None):
-        return self.p(name, buf).view(self.offsets[name][1])
 
     def enc_names(self, i):
         p = _enc(i)
@@ -171,23 +141,6 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
                     w1=p + "feed_forward.intermediate_dense.weight", b1=p + "feed_forward.intermediate_dense.bias",
                     w2=p + "feed_forward.output_dense.weight", b2=p + "feed_forward.output_dense.bias",
                     ln2_w=p + "final_layer_norm.weight", ln2_b=p + "final_layer_norm.bias")
-
-    def named_parameters(self):
-        return [(n, self.view(n)) for n, _ in self.names_shapes]
-
-    def named_grads(self):
-        return [(n, self.view(n, self.grad)) for n, _ in self.names_shapes]
-
-    def state_dict(self):
-        return {n: self.view(n).detach().clone() for n, _ in self.names_shapes}
-
-    def load_state_dict(self, sd, strict=True):
-        for n, s in self.names_shapes:
-            if n in sd:
-                self.view(n).copy_(torch.as_tensor(sd[n]).to(self.device, torch.float32).reshape(s))
-            elif strict:
-                raise KeyError(n)
-        self.refresh_operands()
 
     def init_weights(self, seed=0):
         """HF Wav2Vec2PreTrainedModel._init_weights magnitudes: kaiming-normal conv filters, normal(0, 0.02) dense weights, LayerNorm /
@@ -211,25 +164,19 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
                 sd[n] = torch.randn(s, generator=g) * 0.02
         self.load_state_dict(sd)
 
-    def refresh_operands(self):
-        ops.cast_f32_bf16(self.flat, self.flat_bf16, self.numel)
-        self.refresh_transposed()
+    def transpose_items(self):
+        C, D = self.cfg.conv_dim[0], self.cfg.hidden
+        return super().transpose_items() + [(self.p(M_ + "feature_projection.projection.weight"), True, C, self.projT, D, D, D, C, False)]
 
     def refresh_transposed(self):
+        """+ the bf16 operands of the feature-encoder convolutions and of the weight-normed positional convolution."""
+        super().refresh_transposed()
         cfg = self.cfg
         C, D = cfg.conv_dim[0], cfg.hidden
-        if self._wT_desc is None:
-            items = self.enc_transpose_items()
-            items.append((self.p(M_ + "feature_projection.projection.weight"), True, C, self.projT, D, D, D, C, False))
-            self._wT_desc = ops.make_transpose_desc(items, self.device)
-        ops.transpose_batched(*self._wT_desc)
         for l in range(1, len(cfg.conv_kernel)):
             ops.w2v_conv_weight_prep(self.p(FE + "%d.conv.weight" % l), self.conv_w[l][0], self.conv_w[l][1], C, C, cfg.conv_kernel[l])
         ops.w2v_weightnorm_prep(self.p(PC + "parametrizations.weight.original1"), self.p(PC + "parametrizations.weight.original0"),
                                 self.pos_norms, self.pos_Wf, self.pos_Wb, D, cfg.pos_groups, cfg.pos_k)
-
-    def no_weight_decay(self):
-        return []
 
     def group_matcher(self, coarse=False, prefix=""):
         return dict(stem=r"^{}model.feature_projection|^{}model.feature_extractor".format(prefix, prefix),
@@ -248,23 +195,6 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
             else:
                 ids[n] = L + 1
         return ids, L + 1
-
-    def train(self, mode=True):
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def zero_grad(self):
-        self.grad.zero_()
-
-    def _buf(self, key, shape, dtype, zero=False):
-        t = self._ws.get(key)
-        if t is None or t.shape != torch.Size(shape) or t.dtype != dtype:
-            t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
-            self._ws[key] = t
-        return t
 
     # ---- geometry ---------------------------------------------------------------------------------------------
     def geometry(self, samples):
@@ -296,8 +226,8 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
 
     def _front_buffers(self, B, samples, tag, save):
         key = ("front", B, samples, tag)
-        if key in self._ws:
-            return self._ws[key]
+        if key in self._buf_cache:
+            return self._buf_cache[key]
         cfg = self.cfg
         T, P, Pp = self.geometry(samples)
         C, D, G, cg, k = cfg.conv_dim[0], cfg.hidden, cfg.pos_groups, self.cg, cfg.pos_k
@@ -324,7 +254,7 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
         c.pos_desc = ops.make_group_desc_ld(
             [(ops._pa(c.Xg, g * c.rows_total * cg), cg, ops._pa(self.pos_Wf, g * cg * Kc), Kc, ops._pa(c.conv, g * cg), D, B * Pp, cg, Kc)
              for g in range(G)], dev, bn=64 if cg <= 64 else 128)
-        self._ws[key] = c
+        self._buf_cache[key] = c
         return c
 
     # ---- forward ---------------------------------------------------------------------------------------------------
@@ -386,12 +316,12 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
 
     def _ctx_buffers(self, B, L, tag):
         key = ("ctx", B, L, tag)
-        if key not in self._ws:
+        if key not in self._buf_cache:
             c = types.SimpleNamespace()
             self.enc_alloc_ctx(c, B, L)
             self.head_alloc_ctx(c, B)
-            self._ws[key] = c
-        return self._ws[key]
+            self._buf_cache[key] = c
+        return self._buf_cache[key]
 
     def forward(self, x, only_fc=False, only_feat=False, **kw):
         """Reference-compatible entry (wave2vecv2.py:23-40): x fp32 [B, samples] -> {'logits','feat'}."""
@@ -407,8 +337,8 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
     # ---- backward ---------------------------------------------------------------------------------------------------
     def _bwd_front(self, B, f):
         key = ("bwdfront", B, id(f))
-        if key in self._ws:
-            return self._ws[key]
+        if key in self._buf_cache:
+            return self._buf_cache[key]
         cfg = self.cfg
         C, D, G, cg, k, nl = cfg.conv_dim[0], cfg.hidden, cfg.pos_groups, self.cg, cfg.pos_k, len(cfg.conv_kernel)
         P, Pp = f.P, f.Pp
@@ -463,7 +393,7 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
                               C, kk * C, min(CH, R - r0)))
         t.conv_dw = ops.make_group_tn_desc_ld(probs, dev, tile=256 if t.conv_dw_pp else 128)
         t.ws2 = torch.zeros(B, C, 2, dtype=torch.float64, device=dev)
-        self._ws[key] = t
+        self._buf_cache[key] = t
         return t
 
     def backward(self, ctx, dlogits):

@@ -36,6 +36,8 @@ class WrnContext:
 
 
 class WideResNet(ModuleSurface):
+    couples_batch_rows = True     # BatchNorm: every forward call is its own statistics group (no cross-pass batching)
+
     def __init__(self, num_classes, depth=28, widen_factor=2, first_stride=1, device="cuda", **kw):
         assert (depth - 4) % 6 == 0
         self.num_classes, self.depth, self.widen, self.first_stride = num_classes, depth, widen_factor, first_stride
@@ -54,21 +56,13 @@ class WideResNet(ModuleSurface):
             if cin != cout:
                 s.append((p + "convShortcut.weight", (cout, cin, 1, 1)))
         s += [("bn1.weight", (ch[3],)), ("bn1.bias", (ch[3],)), ("classifier.weight", (num_classes, ch[3])), ("classifier.bias", (num_classes,))]
-        self.names_shapes = s
-        self.offsets, o = {}, 0
-        for nme, shp in s:
-            self.offsets[nme] = (o, shp)
-            o += _round_up(int(torch.Size(shp).numel()), 4)          # 16-byte aligned starts (TN GEMM writes dW in place)
-        self.numel = o
+        self._init_block(s, align=4, bf16=False)          # 16-byte aligned starts (TN GEMM writes dW in place)
         f32 = torch.float32
-        self.flat = torch.zeros(o, dtype=f32, device=self.device)
-        self.grad = torch.zeros(o, dtype=f32, device=self.device)
         self.bn = [(p + "bn1", cin, 1e-5) for p, cin, _, _, _ in self.blocks]       # forward order is interleaved; names only matter
         self.bn = []
         for p, cin, cout, _, _ in self.blocks:
             self.bn += [(p + "bn1", cin, 1e-5), (p + "bn2", cout, 1e-5)]
         self.bn.append(("bn1", ch[3], 1e-3))
-        self.buffers = {}
         for nme, c, _ in self.bn:
             self.buffers[nme + ".running_mean"] = torch.zeros(c, dtype=f32, device=self.device)
             self.buffers[nme + ".running_var"] = torch.ones(c, dtype=f32, device=self.device)
@@ -119,49 +113,6 @@ class WideResNet(ModuleSurface):
         self.conv_stride = {"conv1.weight": 1}
         for p_, _, _, st_, _ in self.blocks:
             self.conv_stride.update({p_ + "conv1.weight": st_, p_ + "conv2.weight": 1, p_ + "convShortcut.weight": st_})
-        self.training = True
-        self.couples_batch_rows = True      # BatchNorm: every forward call is its own statistics group (no cross-pass batching)
-        self._buf_cache = {}
-
-    # ---- parameter plumbing (same surface as the ViT engine) ------------------------------------------------------------------
-    def p(self, name, buf=None):
-        """Flat view of parameter ``name`` inside ``buf`` (default: the parameter block).  Cached per (name, buffer): building a slice view costs
-        ~3 us of host time and a step asks for ~500 of them -- more than half of the step's enqueue time before the cache."""
-        b = self.flat if buf is None else buf
-        if not (b is self.flat or b is self.grad or b is getattr(self, "flat_bf16", None)):
-            o, s = self.offsets[name]                     # some other block (optimizer state, a test's copy): no entry is kept for it
-            return b[o:o + int(torch.Size(s).numel())]
-        pv = self.__dict__.setdefault("_pviews", {})
-        ent = pv.get((name, id(b)))
-        if ent is None:
-            o, s = self.offsets[name]
-            ent = pv[(name, id(b))] = (b, b[o:o + int(torch.Size(s).numel())])     # (holds ``b``: its id stays unique)
-        return ent[1]
-
-    def view(self, name, buf=None):
-        return self.p(name, buf).view(self.offsets[name][1])
-
-    def named_parameters(self):
-        return [(n, self.view(n)) for n, _ in self.names_shapes]
-
-    def named_grads(self):
-        return [(n, self.view(n, self.grad)) for n, _ in self.names_shapes]
-
-    def state_dict(self):
-        d = {n: self.view(n).detach().clone() for n, _ in self.names_shapes}
-        d.update({k: v.detach().clone() for k, v in self.buffers.items()})
-        return d
-
-    def load_state_dict(self, sd, strict=True):
-        for n, s in self.names_shapes:
-            if n in sd:
-                self.view(n).copy_(torch.as_tensor(sd[n]).to(self.device, torch.float32).reshape(s))
-            elif strict:
-                raise KeyError(n)
-        for k in self.buffers:
-            if k in sd:
-                self.buffers[k].copy_(torch.as_tensor(sd[k]).to(self.device))
-        self.refresh_operands()
 
     def init_weights(self, seed=0):
         """wrn.py:108-117: Conv2d kaiming_normal(fan_out, leaky_relu: gain sqrt(2 / (1 + 0.01^2))), BatchNorm 1 / 0, Linear xavier_normal
@@ -199,25 +150,8 @@ class WideResNet(ModuleSurface):
         if self._flip_desc:
             ops.conv_weight_flip_grouped(*self._flip_desc)
 
-    def zero_grad(self):
-        self.grad.zero_()
-
-    def train(self, mode=True):
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
     def no_weight_decay(self):
         return [n for n, _ in self.names_shapes if "bn" in n or "bias" in n]            # wrn.py:143-148
-
-    def _buf(self, key, shape, dtype):
-        t = self._buf_cache.get(key)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            t = torch.empty(shape, dtype=dtype, device=self.device)
-            self._buf_cache[key] = t
-        return t
 
     # ---- forward ----------------------------------------------------------------------------------------------------------------
     def _conv(self, name, act, B, H, W, stride, out, tag, bias=None, resid=None):

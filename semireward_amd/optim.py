@@ -112,7 +112,7 @@ class FusedAdamW:
         ns = model.names_shapes
         hp = layer_decay_hparams(ns, model.cfg.depth, lr, weight_decay, layer_decay, no_weight_decay=tuple(model.no_weight_decay()),
                                  layer_ids=model.layer_ids() if hasattr(model, "layer_ids") else None,
-                                 frozen=tuple(getattr(model, "frozen_params", ())))
+                                 frozen=tuple(model.frozen_params))
         self.lr_t = torch.tensor([h[0] for h in hp], dtype=torch.float32, device=dev)
         self.wd_t = torch.tensor([h[1] for h in hp], dtype=torch.float32, device=dev)
         self.table = build_chunk_table([int(torch.Size(s).numel()) for _, s in ns], offsets=[model.offsets[n][0] for n, _ in ns]).to(dev)
@@ -139,10 +139,7 @@ class FusedAdamW:
                        self.table.shape[0], self.lr_t, self.wd_t, self.lr_factor(), self.step_count, self.betas[0],
                        self.betas[1], self.eps, ema_m=ema_m, grad_scale=grad_scale, zero_grad=True, clip_coef=coef,
                        dyn=sc.adamw_ptr if sc is not None else None)
-        if getattr(self.model, "lazy_transposed", False):
-            self.model._wT_stale = True          # refreshed off the critical path (model.ensure_transposed)
-        else:
-            self.model.refresh_transposed()
+        self.model.params_updated()
         self.sched_step += 1
 
     def state_dict(self):
@@ -187,7 +184,7 @@ class FusedSGD:
         self.model = model
         dev = model.flat.device
         ns = model.names_shapes
-        nwd = set(model.no_weight_decay()) if hasattr(model, "no_weight_decay") else set()
+        nwd = set(model.no_weight_decay())
         ends = [model.offsets[n][0] for n, _ in ns][1:] + [model.numel]          # a parameter's chunk runs to the next one's start
         tab = np.zeros(len(ns), dtype=[("end", "<i8"), ("wd", "<f4"), ("pad", "<f4")])
         for i, (n, shp) in enumerate(ns):

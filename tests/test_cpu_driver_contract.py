@@ -14,7 +14,7 @@ import _driver_replay as R
 from semireward_amd.core.algorithmbase import AlgorithmBase
 from semireward_amd.core.hooks import Hook
 from semireward_amd.core.utils import count_parameters, send_model_cuda
-from semireward_amd.nets import vit
+from semireward_amd.nets import bert, vit, wave2vec, wrn
 
 
 def _args(**kw):
@@ -63,19 +63,38 @@ class _HostOnly(AlgorithmBase):
         return {"loss": torch.zeros(())}, {"train/total_loss": 0.0}
 
 
-def test_count_parameters_and_module_surface():
-    m = vit.VisionTransformer(vit.VitConfig(img_size=32, patch_size=2, embed_dim=384, depth=12, num_heads=6, num_classes=100), device="cpu")
-    n = sum(int(torch.Size(s).numel()) for _, s in m.names_shapes)
-    assert count_parameters(m) == n == 21436900          # ViT-S/2, 100 classes: the number train.py:396 logs for the headline config
+# one backbone per engine family, built on the CPU device (no launch): the flat-block surface they share (nets/surface.py ModuleSurface)
+_SURFACE_NETS = [
+    ("vit", lambda: vit.VisionTransformer(vit.VitConfig(img_size=32, patch_size=2, embed_dim=384, depth=12, num_heads=6, num_classes=100),
+                                          device="cpu")),
+    ("bert", lambda: bert.ClassificationBert(bert.BertConfig(vocab=120, hidden=128, layers=2, heads=2, inter=512, max_pos=64, num_classes=4),
+                                             device="cpu")),
+    ("wave2vec", lambda: wave2vec.ClassificationWave2Vec(wave2vec.W2vConfig(hidden=128, layers=2, heads=2, inter=256, conv_dim=(128, 128, 128),
+                                                                            conv_kernel=(10, 3, 2), conv_stride=(5, 2, 2), pos_k=16, pos_groups=4,
+                                                                            num_classes=4), device="cpu")),
+    ("wrn", lambda: wrn.WideResNet(num_classes=10, depth=10, widen_factor=2, device="cpu")),
+]
+
+
+@pytest.mark.parametrize("family,build", _SURFACE_NETS, ids=[f for f, _ in _SURFACE_NETS])
+def test_count_parameters_and_module_surface(family, build):
+    m = build()
+    n = sum(int(torch.Size(s).numel()) for n_, s in m.names_shapes if n_ not in m.frozen_params)
+    assert count_parameters(m) == n
+    if family == "vit":
+        assert n == 21436900          # ViT-S/2, 100 classes: the number train.py:396 logs for the headline config
     assert sum(p.numel() for p in m.parameters() if p.requires_grad) == n            # the reference's expression verbatim (misc.py:75)
     ps = list(m.parameters())
     assert [tuple(p.shape) for p in ps] == [tuple(s) for _, s in m.names_shapes]      # named_parameters() order and shapes
-    m.grad[m.offsets["head.bias"][0]] = 3.0
-    hb = ps[[n_ for n_, _ in m.names_shapes].index("head.bias")]
-    assert hb.requires_grad and float(hb.grad[0]) == 3.0 and hb.data_ptr() == m.view("head.bias").data_ptr()      # views, not copies
-    assert m.cuda is not None and m.to("cpu") is m and m.to(device="cpu") is m
+    assert [p.requires_grad for p in ps] == [n_ not in m.frozen_params for n_, _ in m.names_shapes]
+    last = m.names_shapes[-1][0]                                                       # every family ends with its classifier's bias
+    m.grad[m.offsets[last][0]] = 3.0
+    assert ps[-1].requires_grad and float(ps[-1].grad[0]) == 3.0 and ps[-1].data_ptr() == m.view(last).data_ptr()      # views, not copies
+    assert m.to("cpu") is m and m.to(device="cpu") is m
     with pytest.raises(RuntimeError, match="cannot be moved"):
         m.to("cuda:0")
+    with pytest.raises(RuntimeError, match="cannot be moved"):
+        m.cuda()
     with pytest.raises(RuntimeError, match="one numeric mode"):
         m.to(torch.float16)
     assert torch.nn.SyncBatchNorm.convert_sync_batchnorm(m) is m          # misc.py:55 walks named_children(): nothing to convert, same object
