@@ -164,7 +164,10 @@ class AlgorithmBase:
         return ld
 
     def set_model(self):
-        model = self.net_builder(num_classes=self.num_classes, device=self.device)
+        # algorithmbase.py:251-254 hands use_pretrain / pretrain_path to the builder; only when set, so two-argument builders keep working
+        a = self.args
+        kw = dict(pretrained=True, pretrained_path=getattr(a, "pretrain_path", None)) if getattr(a, "use_pretrain", False) else {}
+        model = self.net_builder(num_classes=self.num_classes, device=self.device, **kw)
         model.refresh_operands()
         return model
 

@@ -17,8 +17,9 @@ erf-GELU, LayerNorm eps 1e-12, dropout 0.1 in train mode) is a short list of HIP
 and the backward is hand-written (post-LN: the gradient of a LayerNorm input feeds the residual path in fp32 and, dropout-masked, the
 branch's dX / dW products in bf16).  Data layout: B sequences padded to a common L, M = B * L token rows; the residual stream is fp32
 [M, D], GEMM operands bf16; the flat parameter block keeps q/k/v weights (and biases) of a layer adjacent, so the packed [3D, D]
-operand is a VIEW, and a reference checkpoint still maps by name.  ``from_pretrained`` needs the network: weights are random-init
-(HF: normal(0, 0.02), LayerNorm 1/0) or loaded with ``load_state_dict``.
+operand is a VIEW, and a reference checkpoint still maps by name.  ``from_pretrained`` becomes a lookup of the checkpoint on disk
+(nets/pretrained.py: a ``pretrained_path`` directory or the Hugging Face hub cache, never the network); without one the weights are
+random-init (HF: normal(0, 0.02), LayerNorm 1/0).
 
 Padding: batches are right-padded (``tokenizer.pad``, nlp_collactor.py:63-69), so the attention mask is a prefix mask and the engine
 carries ``key_len = mask.sum(1)``; every position -- padding included -- is computed and averaged, exactly like bert.py:36-37.
@@ -28,6 +29,7 @@ import types
 import torch
 
 from .. import ops
+from . import pretrained
 from .encoder import PostLNEncoderMixin
 
 SITE_EMB, SITE_HEAD = 0x7FFFFFF0, 0x7FFFFFF1
@@ -35,9 +37,10 @@ SITE_EMB, SITE_HEAD = 0x7FFFFFF0, 0x7FFFFFF1
 
 class BertConfig:
     def __init__(self, vocab=30522, hidden=768, layers=12, heads=12, inter=3072, max_pos=512, num_classes=2, p_drop=0.1, eps=1e-12,
-                 pad_id=0):
+                 pad_id=0, p_head=None):
         self.vocab, self.hidden, self.layers, self.heads, self.inter, self.max_pos = vocab, hidden, layers, heads, inter, max_pos
         self.num_classes, self.p_drop, self.eps, self.pad_id = num_classes, p_drop, eps, pad_id
+        self.p_head = p_drop if p_head is None else p_head       # dropout before the mean-pool (bert.py:14); a checkpoint's config sets p_drop only
         assert hidden // heads == 64 and hidden in (128, 384, 768), "libsrhip attention is built for head_dim 64"
         assert inter % 32 == 0 and max_pos <= 512
     embed_dim = property(lambda self: self.hidden)
@@ -173,8 +176,8 @@ class ClassificationBert(PostLNEncoderMixin):
         return dict(stem=r"^{}bert.embeddings".format(prefix), blocks=r"^{}bert.encoder.layer.(\d+)".format(prefix))
 
     def next_seed(self):
-        """64-bit dropout seed of one forward call (None in eval mode / p_drop == 0)."""
-        if not self.training or self.cfg.p_drop <= 0.0:
+        """64-bit dropout seed of one forward call (None in eval mode / p_drop == p_head == 0)."""
+        if not self.training or max(self.cfg.p_drop, self.cfg.p_head) <= 0.0:
             return None
         if self.inject_seed is not None:
             return self.inject_seed
@@ -222,7 +225,7 @@ class ClassificationBert(PostLNEncoderMixin):
                          P(E + "token_type_embeddings.weight"), P(E + "LayerNorm.weight"), P(E + "LayerNorm.bias"), cfg.eps, x, xb,
                          ctx.st0[0] if save else None, ctx.st0[1] if save else None, B, L, D, dr(SITE_EMB))
         self.enc_forward(x, xb, ctx, save, B, L, key_len, dr, tag=t)
-        logits, feat = self.head_forward(x, B, L, dr(SITE_HEAD), seq_len, ctx)
+        logits, feat = self.head_forward(x, B, L, dr(SITE_HEAD, cfg.p_head), seq_len, ctx)
         return logits, feat, ctx
 
     def forward(self, x, only_fc=False, only_feat=False, return_embed=False, **kw):
@@ -247,7 +250,7 @@ class ClassificationBert(PostLNEncoderMixin):
         dr = (lambda site, p=cfg.p_drop: ops.Drop(seed, site, p) if p > 0 else None) if seed is not None else (lambda site, p=0.0: None)
         P, G = self.p, (lambda n: self.p(n, self.grad))
         dx = self._buf("b_dx", (M, D), torch.float32)
-        self.head_backward(ctx, dlogits, dx, B, L, dr(SITE_HEAD), ctx.seq_len)
+        self.head_backward(ctx, dlogits, dx, B, L, dr(SITE_HEAD, cfg.p_head), ctx.seq_len)
         self.enc_backward(dx, ctx, B, L, ctx.key_len, dr)
         ops.embed_ln_bwd(dx, ctx.tok.ids, ctx.seq_index, P(E + "word_embeddings.weight"), P(E + "position_embeddings.weight"),
                          P(E + "token_type_embeddings.weight"), ctx.st0[0], ctx.st0[1], P(E + "LayerNorm.weight"),
@@ -255,21 +258,32 @@ class ClassificationBert(PostLNEncoderMixin):
                          G(E + "LayerNorm.weight"), G(E + "LayerNorm.bias"), B, L, D, cfg.pad_id, dr(SITE_EMB))
 
 
-# ---- builders with the reference's names (bert.py:62-69); pretrained checkpoints need the network -> random init -------------
-def _build(num_classes, kw, **cfg):
-    kw = {k: v for k, v in kw.items() if k not in ("pretrained", "pretrained_path")}
+# ---- builders with the reference's names (bert.py:62-69) --------------------------------------------------------------------------------
+def _build(num_classes, kw, hub_name=None, **cfg):
+    """Like the reference's ``BertModel.from_pretrained(name)``, whatever ``pretrained`` says: the encoder starts from the ``pretrained_path``
+    directory or the hub-cache snapshot of ``hub_name`` when one is on disk (nets/pretrained.py), with the dropout of its config.json;
+    the classifier and, when nothing is found, the whole model keep the random init of ``seed``."""
+    kw = dict(kw)
+    kw.pop("pretrained", None)
+    path = kw.pop("pretrained_path", None)
     device = kw.pop("device", "cuda")
-    m = ClassificationBert(BertConfig(num_classes=num_classes, **cfg), device=device)
+    bcfg = BertConfig(num_classes=num_classes, **cfg)
+    found = pretrained.find_hf_weights("ClassificationBert", hub_name, path)
+    if found is not None:
+        pretrained.apply_bert_config(found[0], bcfg, found[2])
+    m = ClassificationBert(bcfg, device=device)
     m.init_weights(kw.pop("seed", 0))
+    if found is not None:
+        pretrained.load_hf(m, found[1], "bert", found[2])
     return m
 
 
 def bert_base_uncased(num_classes=2, **kw):
-    return _build(num_classes, kw, vocab=30522)
+    return _build(num_classes, kw, hub_name="bert-base-uncased", vocab=30522)
 
 
 def bert_base_cased(num_classes=2, **kw):
-    return _build(num_classes, kw, vocab=28996)
+    return _build(num_classes, kw, hub_name="bert-base-cased", vocab=28996)
 
 
 def bert_tiny_test(num_classes=4, **kw):

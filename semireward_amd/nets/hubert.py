@@ -6,7 +6,7 @@ conv, post-LN encoder with LayerDrop -- under the same parameter names, so the e
 ``hubert_tiny`` vectors of tests/golden/w2v.npz, produced by the reference ClassificationHubert on a random-init HubertModel).  The one
 difference on this path is the optimizer grouping: ``group_matcher`` (hubert.py:52-54) puts the positional conv into the stem group.
 """
-from .wave2vec import ClassificationWave2Vec, W2vConfig, M_
+from .wave2vec import ClassificationWave2Vec, M_, build_pretrained
 
 
 class ClassificationHubert(ClassificationWave2Vec):
@@ -22,16 +22,12 @@ class ClassificationHubert(ClassificationWave2Vec):
         return ids, lmax
 
 
-def _build(num_classes, kw, **cfg):
-    kw = {k: v for k, v in kw.items() if k not in ("pretrained", "pretrained_path")}
-    device = kw.pop("device", "cuda")
-    m = ClassificationHubert(W2vConfig(num_classes=num_classes, **cfg), device=device)
-    m.init_weights(kw.pop("seed", 0))
-    return m
+def _build(num_classes, kw, hub_name=None, **cfg):
+    return build_pretrained(ClassificationHubert, "hubert", hub_name, num_classes, kw, **cfg)
 
 
 def hubert_base(num_classes=2, **kw):
-    return _build(num_classes, kw)
+    return _build(num_classes, kw, hub_name="facebook/hubert-base-ls960")
 
 
 def hubert_tiny_test(num_classes=4, **kw):

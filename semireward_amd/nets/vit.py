@@ -20,6 +20,7 @@ import types
 import torch
 
 from .. import ops
+from .pretrained import load_checkpoint
 from .surface import ModuleSurface
 
 
@@ -521,12 +522,15 @@ class VisionTransformer(ModuleSurface):
             ops.gemm_tn_grouped_f32(desc[0], desc[1], desc[2], alpha=1.0, beta=1.0, flops=desc[3], nbytes=desc[4])
 
 
-# ---- builders with the reference's names (vit.py:323-408); pretrained checkpoints need network -> ignored ------------
+# ---- builders with the reference's names (vit.py:323-408); pretrained=True loads pretrained_path as the reference's load_checkpoint does ----
 def _build(num_classes, kw, **cfg):
-    kw = {k: v for k, v in kw.items() if k not in ("pretrained", "pretrained_path")}
+    kw = dict(kw)
+    pretrained, path = kw.pop("pretrained", False), kw.pop("pretrained_path", None)
     device = kw.pop("device", "cuda")
     m = VisionTransformer(VitConfig(num_classes=num_classes, **cfg), device=device)
     m.init_weights(kw.pop("seed", 0))
+    if pretrained:
+        load_checkpoint(m, path)          # a file or the torch-hub cache entry of the URL; not found: random init + one warning line
     return m
 
 

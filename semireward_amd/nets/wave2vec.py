@@ -18,7 +18,8 @@ reference obtains from ``transformers.Wav2Vec2Model`` (facebook/wav2vec2-base-96
 with a hand-written backward through all of it (the feature encoder is trained: ``_requires_grad = False`` at wave2vecv2.py:14 only stops
 HF from marking the INPUT as requiring a gradient).  Frames per clip are fixed by the sample count (64000 -> 199); every activation keeps a
 per-layer frame pitch (see csrc/w2v_ops.hip), the encoder runs on pitch-P rows with key length T, so the single filler frame is masked,
-not averaged and receives zero gradient.  ``from_pretrained`` needs the network: weights are random-init or ``load_state_dict``.
+not averaged and receives zero gradient.  ``from_pretrained`` becomes a lookup of the checkpoint on disk (nets/pretrained.py: a
+``pretrained_path`` directory or the Hugging Face hub cache, never the network); without one the weights are random-init.
 
 Train-mode randomness of the reference (torch dropout, numpy SpecAugment spans, torch.rand LayerDrop) is drawn here from the counter-based
 dropout generator and a per-call numpy Generator; tests inject all three.  LayerDrop is decided once per engine forward (= one launch train
@@ -30,6 +31,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from . import pretrained
 from .encoder import PostLNEncoderMixin
 
 SITE_EMB, SITE_HEAD, SITE_FEATPROJ = 0x7FFFFFF0, 0x7FFFFFF1, 0x7FFFFFF2
@@ -445,17 +447,32 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
         ops.w2v_conv0(3, *a0, None, t.dY0, G(FE + "0.conv.weight"), None, None, B, S, T[0], P[0], C, k0, s0)
 
 
-# ---- builders with the reference's names (wave2vecv2.py:58-60); the pretrained checkpoint needs the network -> random init -------------
-def _build(num_classes, kw, **cfg):
-    kw = {k: v for k, v in kw.items() if k not in ("pretrained", "pretrained_path")}
+# ---- builders with the reference's names (wave2vecv2.py:58-60) ---------------------------------------------------------------------------
+def build_pretrained(cls, family, hub_name, num_classes, kw, **cfg):
+    """Like the reference's ``<Model>.from_pretrained(name)``, whatever ``pretrained`` says: the model starts from the ``pretrained_path``
+    directory or the hub-cache snapshot of ``hub_name`` when one is on disk (nets/pretrained.py), with the dropout, LayerDrop and
+    SpecAugment settings of its config.json; the classifier and, when nothing is found, the whole model keep the random init of ``seed``."""
+    kw = dict(kw)
+    kw.pop("pretrained", None)
+    path = kw.pop("pretrained_path", None)
     device = kw.pop("device", "cuda")
-    m = ClassificationWave2Vec(W2vConfig(num_classes=num_classes, **cfg), device=device)
+    wcfg = W2vConfig(num_classes=num_classes, **cfg)
+    found = pretrained.find_hf_weights(cls.__name__, hub_name, path)
+    if found is not None:
+        pretrained.apply_audio_config(found[0], wcfg, found[2])
+    m = cls(wcfg, device=device)
     m.init_weights(kw.pop("seed", 0))
+    if found is not None:
+        pretrained.load_hf(m, found[1], family, found[2])
     return m
 
 
+def _build(num_classes, kw, hub_name=None, **cfg):
+    return build_pretrained(ClassificationWave2Vec, "wav2vec2", hub_name, num_classes, kw, **cfg)
+
+
 def wave2vecv2_base(num_classes=2, **kw):
-    return _build(num_classes, kw)
+    return _build(num_classes, kw, hub_name="facebook/wav2vec2-base-960h")
 
 
 def wave2vecv2_tiny_test(num_classes=4, **kw):

@@ -15,6 +15,7 @@ is Bn_Controller.freeze_bn ... unfreeze_bn (running statistics untouched).
 import torch
 
 from .. import ops
+from .pretrained import load_checkpoint
 from .surface import ModuleSurface
 
 MOMENTUM, SLOPE = 0.001, 0.1
@@ -541,10 +542,11 @@ class WideResNet(ModuleSurface):
         ops.add_unpad_grouped(*ent_up[1])
 
 
-def wrn_28_2(num_classes=100, **kw):
-    kw = {k: v for k, v in kw.items() if k not in ("pretrained", "pretrained_path")}
-    m = WideResNet(num_classes=num_classes, depth=28, widen_factor=2, first_stride=1, **kw)           # wrn.py:151-155
+def wrn_28_2(num_classes=100, pretrained=False, pretrained_path=None, **kw):
+    m = WideResNet(num_classes=num_classes, depth=28, widen_factor=2, first_stride=1, **kw)           # wrn.py:160-164
     m.init_weights()
+    if pretrained:
+        load_checkpoint(m, pretrained_path)     # a file or the torch-hub cache entry of the URL; not found: random init + one warning line
     return m
 
 
