@@ -263,6 +263,46 @@ int srhip_layernorm_fwd_f32(const float* x, const float* gamma, const float* bet
                             int D, void* stream);
 int srhip_patch_im2col_f32(const float* img, const int* img_index, float* out, int B, int C, int HW, int ps, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Split-bf16 ("bf16x3") kernels of the gradient rows (grad_rows_precision = bf16x3; csrc/precise_bwd.hip, same product scheme as above).
+ *
+ * srhip_attn_fwd_x3_lse: srhip_attn_fwd_x3 that also writes lse fp32 [B,H,N] = rowmax + log(rowsum) of the scaled scores (the backward's
+ *   statistic).  Same requirements.
+ * srhip_gemm_x3: one 128 x 128-tile engine, fp32 operands, fp32 C.
+ *   SRHIP_X3B_NT: C[M,N] = A[M,K] . B[N,K]^T; epilogue SRHIP_X3B_EPI_GELU_PRE only: v = acc + bias, aux_out[m*ldaux+n] = v, C = gelu_erf(v)
+ *     (fc1 of a row that keeps its activations, vit.py:69-72).  lda, ldb >= K.
+ *   SRHIP_X3B_NN: C[M,N] = epi(A[M,K] . B[K,N]) -- the input gradient dY . W with W read from the fp32 parameter block as it is stored.
+ *     SRHIP_X3B_EPI_F32: C = acc;  SRHIP_X3B_EPI_ACC: C += acc;  SRHIP_X3B_EPI_DGELU: C = acc * gelu_erf'(aux[m*ldaux+n]) (exact-erf derivative).
+ *     No bias.  lda >= K, ldb >= N, N % 4 == 0.
+ *   Both: K % 32 == 0, lda, ldb multiples of 4, A and B 16-byte aligned, ldc >= N, any M up to 65535 * 128.
+ * srhip_gemm_tn_x3_grouped: for every entry of a srhip_group_tn_desc table (tile_start in 128 x 128 tiles, flags 0, A, B fp32):
+ *   C[M,N] += A[K,M]^T . B[K,N], dbias[M] += colsum A (dbias may be NULL) -- dW += dY^T X, db += sum of dY over the tokens.  Any K >= 1 (ragged
+ *   token tails are zero-filled); M, N multiples of 4; lda, ldb multiples of 4; 16-byte aligned A, B.  Deterministic: every output element
+ *   and every bias sum is owned by one workgroup.
+ * srhip_attn_bwd_x3: qkv fp32 [B*N, 3*H*64], out / d_out fp32 [B*N, H*64], lse as srhip_attn_fwd_x3_lse wrote it -> dqkv fp32 [B*N, 3*H*64]
+ *   (every element written); delta_ws fp32 [B,H,N] scratch.  S = Q K^T recomputed, P = exp(S scale - lse), delta = rowsum(dO o O),
+ *   dV = P^T dO, dP = dO V^T, dS = P o (dP - delta), dQ = scale dS K, dK = scale dS^T Q, every product bf16x3.  Two launches.  N <= 512.
+ * srhip_layernorm_bwd_part_f32: srhip_layernorm_bwd_part with fp32 dy and an fp32 out (= row_scale * the updated dx; NULL: not written).
+ * srhip_patch_grad_operands_f32: srhip_patch_grad_operands with an fp32 dx_tok.
+ * srhip_scale_rows_f32: out[m, :] = row_scale[m / rows_per_sample] * x[m, :] (row_scale NULL = 1), fp32, D % 4 == 0, 16-byte aligned. */
+enum { SRHIP_X3B_NT = 0, SRHIP_X3B_NN = 1 };
+enum {
+  SRHIP_X3B_EPI_F32 = 0,
+  SRHIP_X3B_EPI_ACC = 1,
+  SRHIP_X3B_EPI_DGELU = 2,
+  SRHIP_X3B_EPI_GELU_PRE = 3
+};
+int srhip_attn_fwd_x3_lse(const float* qkv, float* out, float* lse, int B, int N, int H, float scale, void* stream);
+int srhip_gemm_x3(int layout, int epilogue, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K,
+                  const float* bias, const float* aux, float* aux_out, int ldaux, void* stream);
+int srhip_gemm_tn_x3_grouped(const srhip_group_tn_desc* desc_dev, int n_problems, int total_tiles, void* stream);
+int srhip_attn_bwd_x3(const float* qkv, const float* out, const float* d_out, const float* lse, float* dqkv, float* delta_ws, int B, int N,
+                      int H, float scale, void* stream);
+int srhip_layernorm_bwd_part_f32(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* dx,
+                                 float* part, int n_rep, float* out, const float* row_scale, int rows_per_sample, int M, int D, void* stream);
+int srhip_patch_grad_operands_f32(const float* dx, float* dx_tok, float* dpos, float* dcls, int B, int Np, int D, void* stream);
+int srhip_scale_rows_f32(const float* x, const float* scale, int rows_per_sample, float* out, long M, int D, void* stream);
+
 /* Final norm on the cls token, global_pool='token', classifier head (vit.py:282, :296-305) (K7).
  * feat fp32 [B,D], logits fp32 [B,C]; xhat [B,D] / rstd [B] saved for the backward when non-NULL. */
 int srhip_cls_head_fwd(const float* x, const float* gamma, const float* beta, float eps, const float* Wh, const float* bh,

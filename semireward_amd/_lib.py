@@ -16,6 +16,8 @@ LIB_PATH = os.path.join(HERE, "libsrhip.so")
 
 EPI_BF16, EPI_GELU_BF16, EPI_RESID_F32, EPI_DGELU_BF16, EPI_F32 = range(5)
 X3_EPI_F32, X3_EPI_GELU_F32, X3_EPI_RESID_F32 = range(3)     # srhip_gemm_nt_x3
+X3B_NT, X3B_NN = range(2)                                      # srhip_gemm_x3 layouts
+X3B_EPI_F32, X3B_EPI_ACC, X3B_EPI_DGELU, X3B_EPI_GELU_PRE = range(4)  # srhip_gemm_x3 epilogues
 
 P, I, F, L, Dbl, U = c_void_p, c_int, c_float, c_long, c_double, c_uint
 SIGNATURES = {
@@ -54,6 +56,13 @@ SIGNATURES = {
     "srhip_attn_fwd_x3": (I, [P, P, I, I, I, F, P]),
     "srhip_layernorm_fwd_f32": (I, [P, P, P, F, P, P, P, I, I, P]),
     "srhip_patch_im2col_f32": (I, [P, P, P, I, I, I, I, P]),
+    "srhip_attn_fwd_x3_lse": (I, [P, P, P, I, I, I, F, P]),
+    "srhip_gemm_x3": (I, [I, I, P, I, P, I, P, I, I, I, I, P, P, P, I, P]),
+    "srhip_gemm_tn_x3_grouped": (I, [P, I, I, P]),
+    "srhip_attn_bwd_x3": (I, [P, P, P, P, P, P, I, I, I, F, P]),
+    "srhip_layernorm_bwd_part_f32": (I, [P, P, P, P, P, P, P, I, P, P, I, I, I, P]),
+    "srhip_patch_grad_operands_f32": (I, [P, P, P, P, I, I, I, P]),
+    "srhip_scale_rows_f32": (I, [P, P, I, P, L, I, P]),
     "srhip_cls_head_fwd": (I, [P, P, P, F, P, P, P, P, P, P, I, I, I, I, P]),
     "srhip_cls_head_fwd_scatter": (I, [P, P, P, F, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "srhip_cls_head_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),

@@ -212,6 +212,28 @@ def read_rows_precision(args, net_cls=None):
     return v
 
 
+GRAD_ROWS_PRECISIONS = ("bf16", "bf16x3")
+
+
+def grad_rows_precision(args, net_cls=None):
+    """Numeric mode of the rows that carry the backward (the labelled rows of pass 0, the strong rows of the last pass):
+    ``args.grad_rows_precision``, else the environment variable SR_GRAD_ROWS_PRECISION, else "bf16".
+      bf16   : bf16 GEMM / attention operands and saved activations, the bf16 hand-written backward -- bit for bit the engine's one mode;
+      bf16x3 : split-bf16 products and fp32 activations in the forward AND the backward of those rows (csrc/precise_bwd.hip).
+    Independent of read_rows_precision; both set to bf16x3 give a step that follows the fp32 reference end to end.
+    Raises ValueError for another value, NotImplementedError for bf16x3 on a backbone without that backward (``precise_grad_rows``)."""
+    v = getattr(args, "grad_rows_precision", None)
+    if v is None:
+        v = os.environ.get("SR_GRAD_ROWS_PRECISION", "bf16")
+    v = str(v).strip().lower()
+    if v not in GRAD_ROWS_PRECISIONS:
+        raise ValueError("grad_rows_precision must be one of %s, got %r" % (", ".join(GRAD_ROWS_PRECISIONS), v))
+    if v == "bf16x3" and net_cls is not None and not getattr(net_cls, "precise_grad_rows", False):
+        raise NotImplementedError("grad_rows_precision: bf16x3 is built for the ViT engine only; backbone %s has no split-bf16 backward"
+                                  % getattr(net_cls, "__name__", net_cls))
+    return v
+
+
 class SRConsistencyBase(AlgorithmBase):
     """Shared step of the confidence-threshold SemiReward algorithms (SRFlexMatch, SRFixMatch): the reference classes
     differ only in their MaskingHook and in whether ``train_step`` receives ``idx_ulb``."""
@@ -219,8 +241,12 @@ class SRConsistencyBase(AlgorithmBase):
     def __init__(self, args, net_builder, tb_log=None, logger=None):
         # checked before any device work; a builder whose class cannot be told is checked on the built model below
         self.read_rows_precision = read_rows_precision(args, backbone_class(net_builder))
+        self.grad_rows_precision = grad_rows_precision(args, backbone_class(net_builder))
         super().__init__(args, net_builder, tb_log, logger)
         read_rows_precision(argparse.Namespace(read_rows_precision=self.read_rows_precision), type(self.model))
+        grad_rows_precision(argparse.Namespace(grad_rows_precision=self.grad_rows_precision), type(self.model))
+        if self.grad_rows_precision == "bf16x3":
+            self.model.grad_rows_precision = "bf16x3"        # the opt-in of the backbone's saved split-bf16 forward
         self._init_thresholds(args)
         self.N_k = args.N_k
         # sr_ema != 0 selects EMARewarder in the reference (srflexmatch.py:49-50); its forward is identical and its EMA
@@ -304,6 +330,7 @@ class SRConsistencyBase(AlgorithmBase):
         main = torch.cuda.current_stream()
         side = self._side_stream if self.overlap_grad_rows else None
         dp_grad = sel(pl.grad_cols, 0)
+        gkw = dict(precision="bf16x3") if self.grad_rows_precision == "bf16x3" else {}       # the gradient rows' forward (both branches below)
         ni, nr = pl.inf_cols.numel(), pl.rest_cols.numel()
         if getattr(pl, "x3_cols", None) is not None:
             # read_rows_precision = bf16x3: the columns the step reads run the split-bf16 chain; the unread columns _Plan moved into the
@@ -339,7 +366,7 @@ class SRConsistencyBase(AlgorithmBase):
             with torch.cuda.stream(side), ops.stream_scope():
                 m.ensure_transposed()              # backward-only operands of the new parameters: here they delay nothing
                 lg_g, ft_g, ctx = m.forward_features(imgs, pl.grad_img, dp_grad, save=True,
-                                                     **(dict(out=(logits, feats, pl.grad_cols)) if scatter else {}))
+                                                     **(dict(out=(logits, feats, pl.grad_cols)) if scatter else {}), **gkw)
                 grad_done = torch.cuda.Event()
                 grad_done.record(side)
                 if _PHASES:
@@ -364,9 +391,9 @@ class SRConsistencyBase(AlgorithmBase):
             self._grad_pending = (grad_done, lg_g, ft_g, logits, feats, None if scatter else pl.grad_cols)
             return logits, feats, ctx
         if scatter:
-            _, _, ctx = m.forward_features(imgs, pl.grad_img, dp_grad, save=True, out=(logits, feats, pl.grad_cols))
+            _, _, ctx = m.forward_features(imgs, pl.grad_img, dp_grad, save=True, out=(logits, feats, pl.grad_cols), **gkw)
             return logits, feats, ctx
-        lg_g, ft_g, ctx = m.forward_features(imgs, pl.grad_img, dp_grad, save=True)
+        lg_g, ft_g, ctx = m.forward_features(imgs, pl.grad_img, dp_grad, save=True, **gkw)
         logits.index_copy_(0, pl.grad_cols, lg_g)
         feats.index_copy_(0, pl.grad_cols, ft_g)
         return logits, feats, ctx

@@ -68,12 +68,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 
 // LayerNorm backward: dx (fp32, +=) and dgamma/dbeta (fp32, atomic +=).  4 * RPW rows per workgroup: 32 for the large launches (fewer
 // atomics), 8 for the 4112-row launches of the gradient images (129 workgroups walking 8 dependent rows each left half the chip idle: 21 us).
-template <int NV, int RPW>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x,
+// TDY = float: the fp32-dy instantiation of the bf16x3 gradient rows (srhip_layernorm_bwd_part_f32), whose scaled copy of dx is fp32 too.
+template <int NV, int RPW, typename TDY = bf16_t>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const TDY* __restrict__ dy, const float* __restrict__ x,
                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
                                                     const float* __restrict__ gamma, float* __restrict__ dx,
                                                     float* __restrict__ dgamma, float* __restrict__ dbeta, int M,
-                                                    bf16_t* __restrict__ out_bf16, const float* __restrict__ row_scale, int rows_per_sample,
+                                                    TDY* __restrict__ out_bf16, const float* __restrict__ row_scale, int rows_per_sample,
                                                     float* __restrict__ part, int n_rep) {
   constexpr int D = NV * 128;
   __shared__ float red[2][4][D];
@@ -89,14 +90,19 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
     if (row >= M) break;
     const float mu = mean[row], rs = rstd[row];
     const float2* xr = reinterpret_cast<const float2*>(x + (size_t)row * D);
-    const uint32_t* dr = reinterpret_cast<const uint32_t*>(dy + (size_t)row * D);
     float2 xh[NV], gy[NV];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const float2 xv = xr[i * 64 + lane];
-      const uint32_t d2 = dr[i * 64 + lane];
-      const float d0 = bf2f((bf16_t)(d2 & 0xffff)), d1 = bf2f((bf16_t)(d2 >> 16));
+      float d0, d1;
+      if constexpr (sizeof(TDY) == 4) {
+        const float2 d2 = reinterpret_cast<const float2*>(dy + (size_t)row * D)[i * 64 + lane];
+        d0 = d2.x; d1 = d2.y;
+      } else {
+        const uint32_t d2 = reinterpret_cast<const uint32_t*>(dy + (size_t)row * D)[i * 64 + lane];
+        d0 = bf2f((bf16_t)(d2 & 0xffff)); d1 = bf2f((bf16_t)(d2 >> 16));
+      }
       xh[i] = make_float2((xv.x - mu) * rs, (xv.y - mu) * rs);
       gy[i] = make_float2(d0 * g[i].x, d1 * g[i].y);
       s1 += gy[i].x + gy[i].y;
@@ -116,7 +122,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
       // (was a separate cast_scale_rows launch after every LayerNorm backward: 24 latency-bound launches per step)
       if (out_bf16) {
         const float sc = row_scale ? row_scale[row / rows_per_sample] : 1.0f;
-        reinterpret_cast<uint32_t*>(out_bf16 + (size_t)row * D)[i * 64 + lane] = pack_bf2(o.x * sc, o.y * sc);
+        if constexpr (sizeof(TDY) == 4) reinterpret_cast<float2*>(out_bf16 + (size_t)row * D)[i * 64 + lane] = make_float2(o.x * sc, o.y * sc);
+        else reinterpret_cast<uint32_t*>(out_bf16 + (size_t)row * D)[i * 64 + lane] = pack_bf2(o.x * sc, o.y * sc);
       }
     }
   }
@@ -582,11 +589,16 @@ __global__ void patch_assemble_kernel(const float* __restrict__ tok, const float
 }
 
 // backward operand: the patch-token rows of dx (fp32 [B, N, D], cls row skipped) as bf16 [B * Np, D]
-__global__ void patch_gather_grad_kernel(const float* __restrict__ dx, bf16_t* __restrict__ out, int Np, int D) {
+// TOUT = float: the fp32 dY operand of the bf16x3 filter gradient (srhip_patch_grad_operands_f32)
+template <typename TOUT = bf16_t>
+__global__ void patch_gather_grad_kernel(const float* __restrict__ dx, TOUT* __restrict__ out, int Np, int D) {
   const int p = blockIdx.x, b = blockIdx.y;
   const float* src = dx + ((size_t)b * (Np + 1) + 1 + p) * D;
-  bf16_t* o = out + ((size_t)b * Np + p) * D;
-  for (int d = 2 * threadIdx.x; d < D; d += 2 * blockDim.x) *reinterpret_cast<uint32_t*>(o + d) = pack_bf2(src[d], src[d + 1]);
+  TOUT* o = out + ((size_t)b * Np + p) * D;
+  for (int d = 2 * threadIdx.x; d < D; d += 2 * blockDim.x) {
+    if constexpr (sizeof(TOUT) == 4) *reinterpret_cast<float2*>(o + d) = make_float2(src[d], src[d + 1]);
+    else *reinterpret_cast<uint32_t*>(o + d) = pack_bf2(src[d], src[d + 1]);
+  }
 }
 
 extern "C" int srhip_layernorm_fwd(const float* x, const float* gamma, const float* beta, float eps, void* out,
@@ -846,7 +858,39 @@ extern "C" int srhip_patch_grad_operands(const float* dx, void* dx_tok_bf16, flo
   hipStream_t s = (hipStream_t)stream;
   SR_LAUNCH(patch_embed_bwd_pos_kernel, dim3(Np + 1), dim3(D), 0, s, dx, dpos, dcls, B, Np + 1, D);
   SR_CHECK_LAUNCH();
-  SR_LAUNCH(patch_gather_grad_kernel, dim3(Np, B), dim3(D < 512 ? 64 : 256), 0, s, dx, (bf16_t*)dx_tok_bf16, Np, D);
+  SR_LAUNCH(patch_gather_grad_kernel<bf16_t>, dim3(Np, B), dim3(D < 512 ? 64 : 256), 0, s, dx, (bf16_t*)dx_tok_bf16, Np, D);
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+
+extern "C" int srhip_patch_grad_operands_f32(const float* dx, float* dx_tok, float* dpos, float* dcls, int B, int Np, int D, void* stream) {
+  if (!dx || !dx_tok || !dpos || !dcls || B <= 0 || Np <= 0 || D <= 0 || (D & 1) || D > 1024) return SR_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  SR_LAUNCH(patch_embed_bwd_pos_kernel, dim3(Np + 1), dim3(D), 0, s, dx, dpos, dcls, B, Np + 1, D);
+  SR_CHECK_LAUNCH();
+  SR_LAUNCH(patch_gather_grad_kernel<float>, dim3(Np, B), dim3(D < 512 ? 64 : 256), 0, s, dx, dx_tok, Np, D);
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+
+extern "C" int srhip_layernorm_bwd_part_f32(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* dx,
+                                            float* part, int n_rep, float* out, const float* row_scale, int rows_per_sample, int M, int D,
+                                            void* stream) {
+  if (!dy || !part || n_rep <= 0 || M <= 0 || (D != 128 && D != 384 && D != 512 && D != 768) || (row_scale && rows_per_sample <= 0))
+    return SR_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const bool small = M < 16384;
+  dim3 grid(cdiv(M, small ? 8 : 32)), block(256);
+  const int rps = rows_per_sample > 0 ? rows_per_sample : 1;
+#define LNB(NV)                                                                                                                          \
+  do {                                                                                                                                   \
+    if (small) SR_LAUNCH((ln_bwd_kernel<NV, 2, float>), grid, block, 0, s, dy, x, mean, rstd, gamma, dx, (float*)nullptr, (float*)nullptr, M, \
+                         out, row_scale, rps, part, n_rep);                                                                              \
+    else SR_LAUNCH((ln_bwd_kernel<NV, 8, float>), grid, block, 0, s, dy, x, mean, rstd, gamma, dx, (float*)nullptr, (float*)nullptr, M,     \
+                   out, row_scale, rps, part, n_rep);                                                                                    \
+  } while (0)
+  if (D == 128) LNB(1); else if (D == 512) LNB(4); else if (D == 384) LNB(3); else LNB(6);
+#undef LNB
   SR_CHECK_LAUNCH();
   return SR_OK;
 }

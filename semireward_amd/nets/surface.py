@@ -18,6 +18,7 @@ class ModuleSurface:
     scatter_outputs = False     # forward_features(out=...) writes logits / features at the caller's row numbers (no index_copy_)
     droppath_by_cols = False    # make_droppath(cols=...) lays the DropPath table out in the caller's column order (no index_select)
     precise_rows = False        # forward_features(precision="bf16x3"): split-bf16 products, fp32 activations (read_rows_precision)
+    precise_grad_rows = False   # forward_features(save=True, precision="bf16x3") and its backward (grad_rows_precision)
     couples_batch_rows = False  # BatchNorm: every forward call is its own statistics group (no cross-pass batching)
     takes_tokens = False        # inputs are token batches (dicts of input_ids / attention_mask), not image tensors
     lazy_transposed = False     # after an optimizer step the transposed copies are only marked stale (ensure_transposed)

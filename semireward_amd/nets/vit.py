@@ -74,7 +74,7 @@ _FUSED_MLP_MIN_ROWS = 16384
 class FwdContext:
     """Activations kept by a ``save=True`` forward for the hand-written backward."""
     __slots__ = ("B", "img", "img_index", "dp", "xs", "xmid", "ln1", "ln2", "qkv", "ao", "lse", "pre", "h", "st1", "st2",
-                 "feat", "xhat", "rstd")
+                 "feat", "xhat", "rstd", "precision")
 
 
 class VisionTransformer(ModuleSurface):
@@ -83,6 +83,7 @@ class VisionTransformer(ModuleSurface):
     scatter_outputs = True        # forward_features(out=...) writes logits / features at the caller's row numbers (no index_copy_)
     droppath_by_cols = True       # make_droppath(cols=...) lays the DropPath table out in the caller's column order (no index_select)
     precise_rows = True           # forward_features(precision="bf16x3"): split-bf16 products, fp32 activations (read_rows_precision)
+    precise_grad_rows = True      # forward_features(save=True, precision="bf16x3") + its backward (grad_rows_precision)
     lazy_transposed = True        # the optimizer only marks the transposed weight copies stale (ensure_transposed)
 
     def __init__(self, cfg=None, device="cuda", **kw):
@@ -91,6 +92,9 @@ class VisionTransformer(ModuleSurface):
         self.device = torch.device(device)
         self._init_block(param_names_shapes(cfg), align=1, bf16=True)
         self.grad_ready_cb = None          # callable(lo, hi) or None: see backward() / distributed.DataParallel.install_overlap
+        # "bf16x3": save=True forwards may run the split-bf16 chain (its fp32 context is ~2.5x the bf16 one per batch size: an explicit opt-in,
+        # set by the algorithms from grad_rows_precision)
+        self.grad_rows_precision = "bf16"
         self.wT = {}
         for i in range(cfg.depth):
             for w in self.GEMM_WEIGHTS:
@@ -156,6 +160,7 @@ class VisionTransformer(ModuleSurface):
         f32, bf16 = torch.float32, torch.bfloat16
         mk = lambda shape, dt: [torch.empty(shape, dtype=dt, device=self.device) for _ in range(cfg.depth)]   # noqa: E731
         ctx = FwdContext()
+        ctx.precision = "bf16"
         ctx.xs = mk((M, D), f32) + [torch.empty(M, D, dtype=f32, device=self.device)]
         ctx.xmid, ctx.ln1, ctx.ln2 = mk((M, D), f32), mk((M, D), bf16), mk((M, D), bf16)
         ctx.qkv, ctx.ao, ctx.pre = mk((M, 3 * D), bf16), mk((M, D), bf16), mk((M, Hd), bf16)
@@ -168,15 +173,42 @@ class VisionTransformer(ModuleSurface):
         self._buf_cache[key] = ctx
         return ctx
 
+    def _ctx_buffers_x3(self, B):
+        """Activation buffers of a save=True forward in bf16x3 precision: the same fields as _ctx_buffers, every activation fp32.  Persistent
+        per batch size and apart from the bf16 context's, so a captured step allocates nothing and the two modes never share a buffer."""
+        key = ("ctx3", B)
+        if key in self._buf_cache:
+            return self._buf_cache[key]
+        cfg = self.cfg
+        D, N, H, Hd = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden
+        M = B * N
+        f32 = torch.float32
+        mk = lambda shape: [torch.empty(shape, dtype=f32, device=self.device) for _ in range(cfg.depth)]   # noqa: E731
+        ctx = FwdContext()
+        ctx.precision = "bf16x3"
+        ctx.xs = mk((M, D)) + [torch.empty(M, D, dtype=f32, device=self.device)]
+        ctx.xmid, ctx.ln1, ctx.ln2 = mk((M, D)), mk((M, D)), mk((M, D))
+        ctx.qkv, ctx.ao, ctx.pre, ctx.h = mk((M, 3 * D)), mk((M, D)), mk((M, Hd)), mk((M, Hd))
+        ctx.lse = mk((B, H, N))
+        ctx.st1 = [(t[0], t[1]) for t in mk((2, M))]
+        ctx.st2 = [(t[0], t[1]) for t in mk((2, M))]
+        ctx.xhat = torch.empty(B, D, dtype=f32, device=self.device)
+        ctx.rstd = torch.empty(B, dtype=f32, device=self.device)
+        self._buf_cache[key] = ctx
+        return ctx
+
     # ---- forward ----------------------------------------------------------------------------------
     def forward_features(self, img, img_index=None, droppath=None, save=False, B=None, buftag="", out=None, precision="bf16",
                          kernels_as_images=None):
         """img fp32 [n_img, C, H, W]; img_index int32 [B] (optional gather); droppath fp32 [depth,2,B] or None.
         Returns (logits [B,C], feat [B,D], ctx or None).
-        precision="bf16x3" (rows without a backward only): the split-bf16 chain of _forward_x3 instead of the bf16-operand one.
+        precision="bf16x3": the split-bf16 chain of _forward_x3 instead of the bf16-operand one; with save=True the context keeps fp32
+        activations for the split-bf16 backward (grad_rows_precision).
         kernels_as_images: pick the kernels a launch of that many images would take (rows split off a larger launch keep its results bit for bit)."""
         if precision == "bf16x3":
-            assert not save, "the bf16x3 rows have no backward"
+            if save:
+                assert self.grad_rows_precision == "bf16x3", "a bf16x3 forward with saved activations needs model.grad_rows_precision = 'bf16x3'"
+                return self._forward_x3_save(img, img_index, droppath, B, out)
             return self._forward_x3(img, img_index, droppath, B, buftag, out)
         if precision != "bf16":
             raise ValueError("precision must be 'bf16' or 'bf16x3', got %r" % (precision,))
@@ -341,6 +373,62 @@ class VisionTransformer(ModuleSurface):
         ops.cls_head_fwd(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, None, None, B, N, D, C)
         return logits, feat, None
 
+    def _forward_x3_save(self, img, img_index, droppath, B, out):
+        """_forward_x3 for rows with a backward: the same products and order, every activation kept fp32 in the persistent context of
+        _ctx_buffers_x3 (LayerNorm statistics, the fc1 pre-activation, the attention lse) for backward(ctx.precision = "bf16x3")."""
+        cfg = self.cfg
+        D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
+        B = int(img_index.numel()) if img_index is not None else (B or img.shape[0])
+        M = B * N
+        f32 = torch.float32
+        ctx = self._ctx_buffers_x3(B)
+        ctx.B, ctx.img, ctx.img_index, ctx.dp = B, img, img_index, droppath
+        x = ctx.xs[0]
+        P = self.p
+        Kp = cfg.in_chans * cfg.patch_size ** 2
+        if Kp <= 64:
+            ops.patch_embed_fwd(img, img_index, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("cls_token"),
+                                P("pos_embed"), x, B, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
+        else:
+            Np = N - 1
+            col = self._buf("qcol", (B * Np, Kp), f32)
+            tok = self._buf("qtok", (B * Np, D), f32)
+            ops.patch_im2col_f32(img, img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
+            ops.gemm_nt_x3(ops.X3_EPI_F32, col, P("patch_embed.proj.weight"), tok, B * Np, D, Kp)
+            ops.patch_assemble(tok, P("patch_embed.proj.bias"), P("cls_token"), P("pos_embed"), x, B, Np, D)
+        scale = 64 ** -0.5
+        dst0, dst1 = (droppath.stride(0), droppath.stride(1)) if droppath is not None else (0, 0)
+        for i in range(cfg.depth):
+            b = "blocks.%d." % i
+            s1 = ops.RawRows(droppath, i * dst0) if droppath is not None else None
+            s2 = ops.RawRows(droppath, i * dst0 + dst1) if droppath is not None else None
+            ops.layernorm_fwd_f32(x, P(b + "norm1.weight"), P(b + "norm1.bias"), cfg.eps, ctx.ln1[i], ctx.st1[i][0], ctx.st1[i][1], M, D)
+            ops.gemm_nt_x3(ops.X3_EPI_F32, ctx.ln1[i], P(b + "attn.qkv.weight"), ctx.qkv[i], M, 3 * D, D, bias=P(b + "attn.qkv.bias"))
+            ops.attn_fwd_x3_lse(ctx.qkv[i], ctx.ao[i], ctx.lse[i], B, N, H, scale)
+            xm = ctx.xmid[i]
+            xm.copy_(x)                                 # the residual stream of the block input stays for the LayerNorm backward
+            ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, ctx.ao[i], P(b + "attn.proj.weight"), xm, M, D, D, bias=P(b + "attn.proj.bias"),
+                           row_scale=s1, rows_per_sample=N)
+            ops.layernorm_fwd_f32(xm, P(b + "norm2.weight"), P(b + "norm2.bias"), cfg.eps, ctx.ln2[i], ctx.st2[i][0], ctx.st2[i][1], M, D)
+            ops.gemm_x3(ops.X3B_NT, ops.X3B_EPI_GELU_PRE, ctx.ln2[i], P(b + "mlp.fc1.weight"), ctx.h[i], M, Hd, D, bias=P(b + "mlp.fc1.bias"),
+                        aux_out=ctx.pre[i], ldaux=Hd)
+            xn = ctx.xs[i + 1]
+            xn.copy_(xm)
+            ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, ctx.h[i], P(b + "mlp.fc2.weight"), xn, M, D, Hd, bias=P(b + "mlp.fc2.bias"),
+                           row_scale=s2, rows_per_sample=N)
+            x = xn
+        feat = torch.empty(B, D, dtype=f32, device=self.device)
+        logits = torch.empty(B, C, dtype=f32, device=self.device)
+        ctx.feat = feat
+        if out is not None:
+            logits_all, feats_all, rows = out
+            ops.cls_head_fwd_scatter(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, ctx.xhat,
+                                     ctx.rstd, feats_all, logits_all, rows, B, N, D, C)
+        else:
+            ops.cls_head_fwd(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, ctx.xhat, ctx.rstd,
+                             B, N, D, C)
+        return logits, feat, ctx
+
     def forward(self, x, only_fc=False, only_feat=False, **kw):
         """Reference-compatible entry (vit.py:285-306): returns {'logits','feat'}.  Inference-style call
         (DropPath active only in train mode, no activations kept)."""
@@ -398,7 +486,7 @@ class VisionTransformer(ModuleSurface):
         return out
 
     def backward(self, ctx, dlogits):
-        """Accumulates d(loss)/d(params) into ``self.grad`` given dlogits fp32 [B, C] for a save=True forward."""
+        """Accumulates d(loss)/d(params) into ``self.grad`` given dlogits fp32 [B, C] for a save=True forward (of either precision)."""
         self.backward_rows(ctx, dlogits, 0, ctx.B)
         self.backward_finish(ctx, dlogits)
 
@@ -436,6 +524,8 @@ class VisionTransformer(ModuleSurface):
         (measured in round 5 and not used by the step: profiles/r05_early_sup_backward_ab.txt; backward() runs ONE whole-batch chain).  ``dlogits``
         is the whole [B, C] buffer; only its rows [b0, b1) are read.  LayerNorm / final-norm affine gradients are added with atomics into the
         partial copies; everything that sums over ALL rows -- weight, bias, head and patch-embedding gradients -- is backward_finish."""
+        if ctx.precision == "bf16x3":
+            return self._backward_rows_x3(ctx, dlogits, b0, b1)
         cfg = self.cfg
         D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
         nb = b1 - b0
@@ -485,6 +575,8 @@ class VisionTransformer(ModuleSurface):
         """Everything of the backward that sums over ALL rows, after the chain(s) of backward_rows have covered every image: head weight / bias
         gradients, the LayerNorm partial copies folded into the gradient block, all 4 * depth weight (and bias) gradients in ONE grouped
         launch (dW += dY^T X, db += colsum dY), the patch embedding."""
+        if ctx.precision == "bf16x3":
+            return self._backward_finish_x3(ctx, dlogits)
         cfg = self.cfg
         D, N, C = cfg.embed_dim, cfg.num_tokens, cfg.num_classes
         B = ctx.B
@@ -520,6 +612,137 @@ class VisionTransformer(ModuleSurface):
             ops.patch_im2col(ctx.img, ctx.img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
             ops.patch_grad_operands(dx, dxt, G("pos_embed"), G("cls_token"), B, Np, D)
             ops.gemm_tn_grouped_f32(desc[0], desc[1], desc[2], alpha=1.0, beta=1.0, flops=desc[3], nbytes=desc[4])
+
+    # ---- split-bf16 backward (grad_rows_precision = bf16x3) ------------------------------------------------------------------------------
+    def _bwd_plan_x3(self, M, ctx):
+        """_bwd_plan for a bf16x3 context: fp32 output-gradient buffers per layer, the srhip_gemm_tn_x3_grouped table of all 4 * depth weight
+        (and bias) gradients, the LayerNorm partial copies.  The data-parallel hand-over is one whole-range call after that launch."""
+        key = ("bwdplan3", M, id(ctx))
+        if key in self._buf_cache:
+            return self._buf_cache[key]
+        cfg = self.cfg
+        D, Hd = cfg.embed_dim, cfg.hidden
+        mk = lambda c: torch.empty(M, c, dtype=torch.float32, device=self.device)   # noqa: E731
+        G = lambda n: self.view(n, self.grad)   # noqa: E731
+        layers, problems = [], []
+        for i in range(cfg.depth):
+            b = "blocks.%d." % i
+            t = dict(g2=mk(D), dpre=mk(Hd), g1=mk(D), dqkv=mk(3 * D))
+            layers.append(t)
+            problems += [(t["g2"], ctx.h[i], G(b + "mlp.fc2.weight"), G(b + "mlp.fc2.bias"), D, Hd, M),
+                         (t["dpre"], ctx.ln2[i], G(b + "mlp.fc1.weight"), G(b + "mlp.fc1.bias"), Hd, D, M),
+                         (t["g1"], ctx.ao[i], G(b + "attn.proj.weight"), G(b + "attn.proj.bias"), D, D, M),
+                         (t["dqkv"], ctx.ln1[i], G(b + "attn.qkv.weight"), G(b + "attn.qkv.bias"), 3 * D, D, M)]
+        out = dict(layers=layers, desc=ops.make_group_tn_x3_desc(problems, self.device))
+        out["ln_part"] = torch.zeros(2 * cfg.depth, LN_REP, 2, D, dtype=torch.float32, device=self.device)
+        out["ln_desc"] = ops.make_ln_reduce_desc([(G("blocks.%d.norm%d.weight" % (i, j)), G("blocks.%d.norm%d.bias" % (i, j)))
+                                                  for i in range(cfg.depth) for j in (1, 2)], self.device)
+        names = [n for n, _ in self.names_shapes if n.startswith("blocks.")]
+        out["flat"] = (min(self.offsets[n][0] for n in names), max(self.offsets[n][0] + int(torch.Size(self.offsets[n][1]).numel()) for n in names))
+        self._buf_cache[key] = out
+        return out
+
+    def _bwd_views_x3(self, ctx, T, b0, b1):
+        """_bwd_views for a bf16x3 context (fp32 workspaces of their own)."""
+        key = ("bwdviews3", id(ctx), b0, b1)
+        v = self._buf_cache.get(key)
+        if v is not None:
+            return v
+        cfg = self.cfg
+        D, N, H = cfg.embed_dim, cfg.num_tokens, cfg.num_heads
+        B = ctx.B
+        M = B * N
+        f32 = torch.float32
+        r = lambda t: t[b0 * N:b1 * N]          # noqa: E731
+        im = lambda t: t[b0:b1]                 # noqa: E731
+        v = types.SimpleNamespace()
+        v.dx, v.dln, v.dao = r(self._buf("b3_dx", (M, D), f32)), r(self._buf("b3_dln", (M, D), f32)), r(self._buf("b3_dao", (M, D), f32))
+        v.delta = im(self._buf("b3_delta", (B, H, N), f32))
+        v.xhat, v.rstd = im(ctx.xhat), im(ctx.rstd)
+        v.layers = []
+        for i in range(cfg.depth):
+            Ti = T["layers"][i]
+            v.layers.append(types.SimpleNamespace(
+                g2=r(Ti["g2"]), dpre=r(Ti["dpre"]), g1=r(Ti["g1"]), dqkv=r(Ti["dqkv"]), pre=r(ctx.pre[i]), xmid=r(ctx.xmid[i]), xs=r(ctx.xs[i]),
+                st1=(r(ctx.st1[i][0]), r(ctx.st1[i][1])), st2=(r(ctx.st2[i][0]), r(ctx.st2[i][1])), qkv=r(ctx.qkv[i]), ao=r(ctx.ao[i]),
+                lse=im(ctx.lse[i])))
+        self._buf_cache[key] = v
+        return v
+
+    def _backward_rows_x3(self, ctx, dlogits, b0, b1):
+        """backward_rows of a bf16x3 context: the same chain with fp32 gradients, every input-gradient product dY . W a split-bf16 NN product
+        on the fp32 parameter block (no transposed copies), the attention backward and the LayerNorm backward on fp32 operands."""
+        cfg = self.cfg
+        D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
+        nb = b1 - b0
+        M = nb * N
+        P = self.p
+        G = lambda n: self.p(n, self.grad)   # noqa: E731
+        T = self._bwd_plan_x3(ctx.B * N, ctx)
+        v = self._bwd_views_x3(ctx, T, b0, b1)
+        dl = dlogits if (b0 == 0 and b1 == ctx.B) else dlogits[b0:b1]
+        self._groups_launched = False
+        v.dx.zero_()
+        ops.cls_head_bwd(dl, P("head.weight"), P("norm.weight"), None, v.xhat, v.rstd, v.dx, None, None, G("norm.weight"), G("norm.bias"),
+                         nb, N, D, C)
+        scale = 64 ** -0.5
+        dp = ctx.dp
+        lnp = T["ln_part"]
+        dpr = (lambda i_, j_: ops.RawRows(dp, i_ * dp.stride(0) + j_ * dp.stride(1) + b0)) if dp is not None else (lambda i_, j_: None)
+        L = v.layers
+        ops.scale_rows_f32(v.dx, dpr(cfg.depth - 1, 1), N, L[cfg.depth - 1].g2, M, D)
+        NN = ops.X3B_NN
+        for i in reversed(range(cfg.depth)):
+            b = "blocks.%d." % i
+            Li = L[i]
+            # MLP branch: g2 = s2 * dx; dpre = (g2 . W_fc2) * gelu'(pre); dln2 = dpre . W_fc1
+            ops.gemm_x3(NN, ops.X3B_EPI_DGELU, Li.g2, P(b + "mlp.fc2.weight"), Li.dpre, M, Hd, D, aux=Li.pre, ldaux=Hd)
+            ops.gemm_x3(NN, ops.X3B_EPI_F32, Li.dpre, P(b + "mlp.fc1.weight"), v.dln, M, D, Hd)
+            ops.layernorm_bwd_part_f32(v.dln, Li.xmid, Li.st2[0], Li.st2[1], P(b + "norm2.weight"), v.dx, lnp[2 * i + 1], LN_REP,
+                                       Li.g1, dpr(i, 0), N, M, D)
+            # attention branch: g1 = s1 * dx; dao = g1 . W_proj; dqkv; dln1 = dqkv . W_qkv
+            ops.gemm_x3(NN, ops.X3B_EPI_F32, Li.g1, P(b + "attn.proj.weight"), v.dao, M, D, D)
+            ops.attn_bwd_x3(Li.qkv, Li.ao, v.dao, Li.lse, Li.dqkv, v.delta, nb, N, H, scale)
+            ops.gemm_x3(NN, ops.X3B_EPI_F32, Li.dqkv, P(b + "attn.qkv.weight"), v.dln, M, D, 3 * D)
+            ops.layernorm_bwd_part_f32(v.dln, Li.xs, Li.st1[0], Li.st1[1], P(b + "norm1.weight"), v.dx, lnp[2 * i], LN_REP,
+                                       L[i - 1].g2 if i > 0 else None, dpr(i - 1, 1) if i > 0 else None, N, M, D)
+
+    def _backward_finish_x3(self, ctx, dlogits):
+        """backward_finish of a bf16x3 context: head, LayerNorm fold, ONE srhip_gemm_tn_x3_grouped launch for all 4 * depth weight and bias
+        gradients, the data-parallel hand-over of the blocks' range in one piece, the patch embedding (fp32 kernel or a one-problem x3 table)."""
+        cfg = self.cfg
+        D, N, C = cfg.embed_dim, cfg.num_tokens, cfg.num_classes
+        B = ctx.B
+        M = B * N
+        f32 = torch.float32
+        G = lambda n: self.p(n, self.grad)   # noqa: E731
+        T = self._bwd_plan_x3(M, ctx)
+        dx = self._buf("b3_dx", (M, D), f32)
+        ops.cls_head_bwd(dlogits, None, None, ctx.feat, None, None, None, G("head.weight"), G("head.bias"), None, None, B, N, D, C)
+        ops.ln_grad_reduce(T["ln_desc"], T["ln_part"], 2 * cfg.depth, LN_REP, D)
+        desc, npb, ntiles, flops, nbytes = T["desc"]
+        ops.gemm_tn_x3_grouped(desc, npb, ntiles, flops=flops, nbytes=nbytes)
+        if self.grad_ready_cb is not None:
+            self.grad_ready_cb(*T["flat"])
+        self._groups_launched = False
+        Kp = cfg.in_chans * cfg.patch_size ** 2
+        if Kp <= 64:
+            ws = self._buf("b_pe_ws", (ops.patch_embed_bwd_ws_floats(B, cfg.in_chans, cfg.img_size, cfg.patch_size, D),), f32)
+            ops.patch_embed_bwd_ws(dx, ctx.img, ctx.img_index, G("patch_embed.proj.weight"), G("patch_embed.proj.bias"), G("cls_token"),
+                                   G("pos_embed"), ws, B, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
+        else:                                       # dWp += dx_tok^T col, dbp += colsum dx_tok (one-problem x3 table); dpos, dcls
+            Np = N - 1
+            key = ("pebwd3", B)
+            if key not in self._buf_cache:
+                col = torch.empty(B * Np, Kp, dtype=f32, device=self.device)
+                dxt = torch.empty(B * Np, D, dtype=f32, device=self.device)
+                gw = self.view("patch_embed.proj.weight", self.grad).view(D, Kp)
+                desc = ops.make_group_tn_x3_desc([(dxt, col, gw, self.view("patch_embed.proj.bias", self.grad), D, Kp, B * Np)], self.device)
+                self._buf_cache[key] = (col, dxt, desc)
+            col, dxt, desc = self._buf_cache[key]
+            ops.patch_im2col_f32(ctx.img, ctx.img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
+            ops.patch_grad_operands_f32(dx, dxt, G("pos_embed"), G("cls_token"), B, Np, D)
+            ops.gemm_tn_x3_grouped(desc[0], desc[1], desc[2], flops=desc[3], nbytes=desc[4])
 
 
 # ---- builders with the reference's names (vit.py:323-408); pretrained=True loads pretrained_path as the reference's load_checkpoint does ----

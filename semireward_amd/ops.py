@@ -7,6 +7,7 @@ import torch
 from . import _lib
 from ._lib import EPI_BF16, EPI_DGELU_BF16, EPI_F32, EPI_GELU_BF16, EPI_RESID_F32  # noqa: F401
 from ._lib import X3_EPI_F32, X3_EPI_GELU_F32, X3_EPI_RESID_F32  # noqa: F401
+from ._lib import X3B_NT, X3B_NN, X3B_EPI_F32, X3B_EPI_ACC, X3B_EPI_DGELU, X3B_EPI_GELU_PRE  # noqa: F401
 
 
 # Argument checks cost 0.3 us per pointer x ~4500 pointers per training step = 1.3 ms of host time, which is what bounds the step once the GPU
@@ -601,6 +602,69 @@ def layernorm_fwd_f32(x, gamma, beta, eps, out, mean, rstd, M, D):
 
 def patch_im2col_f32(img, img_index, out, B, C, HW, ps):
     _call("srhip_patch_im2col_f32", _p(img), _p(img_index), _p(out), B, C, HW, ps, _s())
+
+
+# ---- split-bf16 (bf16x3) gradient rows (csrc/precise_bwd.hip) ---------------------------------------------------------------------------
+def attn_fwd_x3_lse(qkv, out, lse, B, N, H, scale):
+    """attn_fwd_x3 that also writes lse fp32 [B, H, N] for attn_bwd_x3 (srhip_attn_fwd_x3_lse)."""
+    args = (_p(qkv), _p(out), _p(lse), B, N, H, scale, _s())
+    if _PROFILE is not None:
+        _PROFILE.timed("srhip_attn_fwd_x3_lse", args, 4.0 * B * H * N * N * 64, "attn_fwd_x3_lse_kernel", 4.0 * B * N * 4 * H * 64)
+        return
+    _call("srhip_attn_fwd_x3_lse", *args)
+
+
+def gemm_x3(layout, epi, A, B, C, M, N, K, *, lda=None, ldb=None, ldc=None, bias=None, aux=None, aux_out=None, ldaux=0):
+    """X3B_NT: C[M,N] = gelu(A[M,K] . B[N,K]^T + bias), aux_out = the pre-activation (X3B_EPI_GELU_PRE).
+    X3B_NN: C[M,N] = epi(A[M,K] . B[K,N]) with epi F32 (=), ACC (+=) or DGELU (* gelu'(aux)).  fp32 operands as bf16 hi / lo planes."""
+    ldb = ldb or (K if layout == X3B_NT else N)
+    args = (layout, epi, _p(A), lda or K, _p(B), ldb, _p(C), ldc or N, M, N, K, _p(bias), _p(aux), _p(aux_out), ldaux, _s())
+    if _PROFILE is not None:        # flops: the fp32-equivalent product; bytes: fp32 operands once + C (+ aux / C read)
+        extra = 1 if (epi == X3B_EPI_ACC or aux is not None or aux_out is not None) else 0
+        _PROFILE.timed("srhip_gemm_x3", args, 2.0 * M * N * K, "gemm_x3_kernel<%s, %d>" % ("nt" if layout == X3B_NT else "nn", epi),
+                       4.0 * (M * K + N * K) + 4.0 * M * N * (1 + extra))
+        return
+    _call("srhip_gemm_x3", *args)
+
+
+def gemm_tn_x3_grouped(desc, n_problems, total_tiles, flops=0.0, nbytes=0.0):
+    """C_p += A_p^T . B_p, dbias_p += colsum A_p for every problem of a make_group_tn_desc table (fp32 A, B; 128-tiles, no split_k)."""
+    args = (_p(desc), n_problems, total_tiles, _s())
+    if _PROFILE is not None:
+        _PROFILE.timed("srhip_gemm_tn_x3_grouped", args, flops, "gemm_tn_x3_grouped_kernel", nbytes)
+        return
+    _call("srhip_gemm_tn_x3_grouped", *args)
+
+
+def make_group_tn_x3_desc(problems, device):
+    """The srhip_group_tn_desc table of gemm_tn_x3_grouped: problems (A fp32 [K,M], B fp32 [K,N], C fp32 [M,N], dbias fp32 [M] or None, M, N,
+    K); returns (desc, n, total_tiles, flops, fp32 algorithmic bytes)."""
+    desc, n, tiles, flops, _ = make_group_tn_desc(problems, device)
+    nbytes = float(sum(4.0 * (M * K + N * K) + 8.0 * M * N for *_, M, N, K in problems))
+    return desc, n, tiles, flops, nbytes
+
+
+def attn_bwd_x3(qkv, out, d_out, lse, dqkv, delta_ws, B, N, H, scale):
+    """dqkv fp32 [B*N, 3*H*64] of softmax(Q K^T scale) V from the fp32 forward state and d_out fp32 (srhip_attn_bwd_x3)."""
+    args = (_p(qkv), _p(out), _p(d_out), _p(lse), _p(dqkv), _p(delta_ws), B, N, H, scale, _s())
+    if _PROFILE is not None:        # flops: S twice, dP twice, dQ, dK, dV; bytes: qkv, out, d_out in, dqkv out
+        _PROFILE.timed("srhip_attn_bwd_x3", args, 14.0 * B * H * N * N * 64, "attn_bwd_x3_kernels", 4.0 * B * N * H * 64 * 8)
+        return
+    _call("srhip_attn_bwd_x3", *args)
+
+
+def layernorm_bwd_part_f32(dy, x, mean, rstd, gamma, dx, part, n_rep, out, row_scale, rows_per_sample, M, D):
+    """layernorm_bwd_part with fp32 dy; out (fp32 or None) = row_scale * the updated dx."""
+    _call("srhip_layernorm_bwd_part_f32", _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx), _p(part), n_rep, _p(out), _p(row_scale),
+          rows_per_sample, M, D, _s())
+
+
+def patch_grad_operands_f32(dx, dx_tok, dpos, dcls, B, Np, D):
+    _call("srhip_patch_grad_operands_f32", _p(dx), _p(dx_tok), _p(dpos), _p(dcls), B, Np, D, _s())
+
+
+def scale_rows_f32(x, scale, rows_per_sample, out, M, D):
+    _call("srhip_scale_rows_f32", _p(x), _p(scale), rows_per_sample, _p(out), M, D, _s())
 
 
 def cls_head_fwd_scatter(x, gamma, beta, eps, Wh, bh, feat, logits, xhat, rstd, feat_all, logits_all, out_rows, B, N, D, C):
