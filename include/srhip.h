@@ -48,6 +48,12 @@ int srhip_gemm_nt(int epilogue, const void* A, int lda, const void* B, int ldb, 
 #define SRHIP_GEMM_PLAN_BIG2WG 4
 #define SRHIP_GEMM_PLAN_PP256 5      /* 256 x 256 x 64 tiles, two wave groups half a phase apart (K % 64 == 0, operands < 2 GiB); else BIG256 = its lockstep predecessor */
 int srhip_gemm_nt_plan(int epilogue, int M, int N, int K, float beta);
+/* srhip_gemm_nt with the tile kernel chosen for a launch of plan_M >= M rows (srhip_gemm_nt_plan(epilogue, plan_M, ...)) and launched over the
+ * M real rows: rows split off a larger launch keep that launch's kernel, so each row's result is the same bit for bit (share_pass_prefixes).
+ * The split-K accumulating product (SRHIP_EPI_F32 with beta = 1) is refused. */
+int srhip_gemm_nt_planned(int epilogue, const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
+                          const float* bias, const float* row_scale, int rows_per_sample, const void* aux_in, void* aux_out,
+                          int ldaux, float alpha, float beta, int plan_M, void* stream);
 /* Launches of fewer than n 128 x 128 tiles go to the 64 x 64 deep-ring kernel (default 256 = one round of the chip; K >= 768 products at N >= 768
  * excepted).  The small tiles are the latency choice for a chain of dependent launches that has the chip to itself; a training step whose
  * row-streaming inference launches own most CUs meanwhile sets a low n (fewer, fatter workgroups).  n < 0: query only.  Returns the previous value.
@@ -340,6 +346,20 @@ int srhip_droppath_fill(float* out, const float* probs, int depth, int B, unsign
  * takes a contiguous column slice -- instead of an index_select per train on the step's critical path. */
 int srhip_droppath_fill_cols(float* out, const float* probs, const long long* cols, int depth, int B, int n_cols, unsigned long long seed,
                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Pass-prefix sharing of ViT inference rows (share_pass_prefixes, csrc/pass_tree.hip).  The K + 1 passes of a step forward the same images
+ * and differ only by their DropPath draws: each (image, draws so far) is computed once, as a node of a pass-prefix tree.
+ *   srhip_vit_fork:   in front of the block where nodes split, node dst0 + g (g < n_new) becomes a copy of node parent[g] < dst0: the fp32
+ *                     residual x [*, rows_per_node, D] and, if ln != NULL, the bf16 norm1 output ln [*, rows_per_node, D] the previous fused
+ *                     launch already wrote.  In place: sources and destinations are disjoint.
+ *   srhip_vit_fanout: after the head, column g (g < n_cols) of the step's tables takes its node's outputs:
+ *                     logits_all[col_rows[g], :C] = node_logits[col_node[g], :], feat_all[col_rows[g], :D] = node_feat[col_node[g], :]
+ *                     (node tables [n_nodes, .], step tables [rows_all, .]).
+ * Index entries out of range copy nothing.  Pure copies (16-byte accesses where slabs and bases allow): results are the unshared launch's. */
+int srhip_vit_fork(float* x, void* ln, const int* parent, int n_new, int dst0, int rows_per_node, int D, void* stream);
+int srhip_vit_fanout(const float* node_logits, const float* node_feat, int n_nodes, const int* col_node, const long long* col_rows,
+                     int n_cols, float* logits_all, float* feat_all, long long rows_all, int C, int D, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Score filter (K8, K9, K11, K12, K13).

@@ -17,6 +17,7 @@ What is restructured for MI355X -- results are unchanged because ViT rows are in
 import argparse
 import os
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -101,17 +102,37 @@ class _Plan:
     """Row bookkeeping of one step: every column is one (pass, image) row of the batched forward; ``grad_cols`` are the
     rows whose logits enter the loss (they are run with activations kept), all other rows run in inference mode."""
 
-    def __init__(self, cols_img, grad_cols, device, skip_cols=(), read_cols=None, rows_per_col=None, defer_fraction=None, split_read=False):
+    def __init__(self, cols_img, grad_cols, device, skip_cols=(), read_cols=None, rows_per_col=None, defer_fraction=None, split_read=False,
+                 whole_images=False):
         """read_cols: the inference columns whose logits / features the step actually READS (weak rows of every pass).  The others are
         computed because the reference computes them (the strong and labelled rows of the passes whose loss is thrown away) -- same
         launches, but nothing waits for them: they run on the second stream behind the gradient rows (``rest``).
         split_read (read_rows_precision = bf16x3): the read launch becomes two -- the columns that are read (``x3``) and the unread ones moved
-        into it below for tile balance (``mix``, bf16 as before) -- and the launch order (perm_cols) is gradient | x3 | mix | deferred."""
+        into it below for tile balance (``mix``, bf16 as before) -- and the launch order (perm_cols) is gradient | x3 | mix | deferred.
+        whole_images (share_pass_prefixes): the deferred columns moved into the read launch are all the deferred columns of whole images, so
+        that the passes of an image stay in one launch train and share their rows there (_PassTree).  The trains then differ in size from the
+        default plan's: _plan_for_sharing keeps such a plan only where no column changes kernels."""
         gset = set(grad_cols) | set(skip_cols)
         inf_all = [c for c in range(len(cols_img)) if c not in gset]
         rset = set(inf_all) if read_cols is None else set(read_cols)
         inf_cols = [c for c in inf_all if c in rset]
         rest_cols = [c for c in inf_all if c not in rset]
+
+        def move(inf_cols, rest_cols, nmove):
+            moved = rest_cols[-nmove:]
+            if whole_images:
+                by_img = {}
+                for c in reversed(rest_cols):                    # images in the order of their last deferred column, from the end
+                    by_img.setdefault(cols_img[c], []).append(c)
+                moved = []
+                for cs in by_img.values():
+                    if len(moved) >= nmove:
+                        break
+                    moved += cs
+                if len(moved) >= len(rest_cols) > nmove:
+                    moved = rest_cols[-nmove:]
+            ms = set(moved)
+            return sorted(inf_cols + moved), [c for c in rest_cols if c not in ms]
         if rest_cols and rows_per_col:
             # tile quantisation of the deferred launch: its row-streaming kernels own a CU per 128-row tile (fused MLP: 147 KB of LDS), so
             # 128 images x 257 tokens = 257 tiles would be TWO rounds on 256 CUs, the second one a single tile.  A few columns more in the
@@ -119,7 +140,7 @@ class _Plan:
             over = (-(-len(rest_cols) * rows_per_col // 128)) % 256
             if 0 < over <= 8:
                 nmove = min(-(-over * 128 // rows_per_col), len(rest_cols) - 1)
-                inf_cols, rest_cols = sorted(inf_cols + rest_cols[-nmove:]), rest_cols[:-nmove]
+                inf_cols, rest_cols = move(inf_cols, rest_cols, nmove)
             # How many of the inference images are deferred (SR_DEFER_FRACTION).  The workgroups of the row-streaming kernels own a CU
             # outright (147 KB of LDS, all registers) for ~100 us: while a deferred launch fills the chip, every small launch of the critical
             # chain (masks, rewards, losses, the backward of the 16 gradient images) waits for one of them to retire.  Deferring a little
@@ -133,7 +154,7 @@ class _Plan:
             keep = int(frac * (len(inf_cols) + len(rest_cols)))
             if 0.0 < frac < 1.0 and (tiles <= 256 or defer_fraction is not None) and 0 < keep < len(rest_cols):
                 nmove = len(rest_cols) - keep
-                inf_cols, rest_cols = sorted(inf_cols + rest_cols[-nmove:]), rest_cols[:-nmove]
+                inf_cols, rest_cols = move(inf_cols, rest_cols, nmove)
         if rest_cols and rows_per_col and len(rest_cols) * rows_per_col < _vit._FUSED_MLP_MIN_ROWS:
             # a deferred launch below the size from which the fused row-streaming kernels are used (nets/vit.py _FUSED_MLP_MIN_ROWS) would
             # run different kernels than the same rows do inside a large launch: it rides in the launch that is read (elide mode: 8 images)
@@ -147,16 +168,22 @@ class _Plan:
         self.rest_img = t([cols_img[c] for c in rest_cols], torch.int32)
         self.ncols = len(cols_img)
         self.x3_cols = self.x3_img = self.mix_cols = self.mix_img = None
+        # host copies of the column lists (share_pass_prefixes builds each launch train's pass-prefix tree on the host)
+        self.cols_img_host = list(cols_img)
+        self.host_cols = dict(inf=list(inf_cols), rest=list(rest_cols))
+        self.perm_host = list(grad_cols) + list(inf_cols) + list(rest_cols)
         if split_read:
             x3 = [c for c in inf_cols if c in rset]
             mix = [c for c in inf_cols if c not in rset]
             self.x3_cols, self.x3_img = t(x3, torch.int64), t([cols_img[c] for c in x3], torch.int32)
             self.mix_cols, self.mix_img = t(mix, torch.int64), t([cols_img[c] for c in mix], torch.int32)
             self.perm_cols = t(list(grad_cols) + x3 + mix + list(rest_cols), torch.int64)
+            self.host_cols.update(x3=x3, mix=mix)
+            self.perm_host = list(grad_cols) + x3 + mix + list(rest_cols)
 
     @classmethod
     def cat_passes(cls, nl, nu, K, device, extra_pass0_strong=False, lb_every_pass=True, defer_unread=False, rows_per_col=None,
-                   elide_unread=False, defer_fraction=None, split_read=False):
+                   elide_unread=False, defer_fraction=None, split_read=False, whole_images=False):
         """use_cat layout of SRFlexMatch / SRFixMatch: every pass is cat(x_lb, x_ulb_w, x_ulb_s); gradients flow from the
         labelled rows of pass 0 and the strong rows of the last pass.  lb_every_pass=False (use_cat=False, the usb_nlp / usb_audio
         configs): data_generator forwards only x_ulb_s and x_ulb_w (srflexmatch.py:83-90), so the labelled columns of the passes
@@ -173,9 +200,153 @@ class _Plan:
             skip = sorted(set(skip) | {k * Bt + j for k in range(1, K + 1) for j in range(nl)} |
                           {k * Bt + j for k in range(1, K) for j in range(nl + nu, Bt)})
         read = [k * Bt + j for k in range(K + 1) for j in range(nl, nl + nu)] if defer_unread else None      # the weak rows
-        p = cls(cols_img, grad, device, skip, read, rows_per_col, defer_fraction, split_read)
+        p = cls(cols_img, grad, device, skip, read, rows_per_col, defer_fraction, split_read, whole_images)
         p.P, p.Bt = K + 1, Bt
         return p
+
+
+class _PassTree:
+    """Pass-prefix tree of one no-save launch train (share_pass_prefixes).  The train's columns are (pass, image) rows; two columns of one image
+    compute bit-identical rows until the first block where their DropPath draws differ.  Level b's nodes are the distinct (image, draws of the
+    blocks <= b, both branches); each is computed once.
+
+    imgs: the image of every column of the train (host ints, train order); codes: int [depth, n], equal codes in block b <=> equal DropPath
+    scales of both branches in block b (None: no DropPath, one node per image throughout).
+
+    Slots: level -1 is the distinct images in order of first appearance (uimg; the patch embedding runs on them).  At level b every node keeps
+    the slot of its parent if it is that parent's first child (by first column), the other children are appended behind the previous level's
+    nodes -- so the fork in front of block b copies only the new nodes (parent slot < level_n[b - 1] <= new slot: in place, no overlap) and a
+    block where nothing splits needs no copy.  Per level: parent[b] (slot at level b - 1), rep[b] (a representative column: the node's DropPath
+    scales are that column's entries of the step's table), level_n[b]; col_node: each column's slot at the last block."""
+
+    def __init__(self, imgs, codes, depth):
+        imgs = np.asarray(imgs, dtype=np.int64)
+        self.n, self.depth = int(imgs.shape[0]), depth
+        u, first, inv = np.unique(imgs, return_index=True, return_inverse=True)
+        order = np.argsort(first, kind="stable")
+        rank = np.empty_like(order)
+        rank[order] = np.arange(order.shape[0])
+        self.uimg = u[order]
+        self.U = int(self.uimg.shape[0])
+        slot = rank[inv.reshape(-1)]
+        prev = self.U
+        self.parent, self.rep, self.level_n = [], [], []
+        for b in range(depth):
+            if codes is None:
+                par = np.arange(prev, dtype=np.int64)
+                rep = np.unique(slot, return_index=True)[1].astype(np.int64)      # first column of every slot
+                self.parent.append(par); self.rep.append(rep); self.level_n.append(prev)
+                continue
+            cb = np.asarray(codes[b], dtype=np.int64)
+            nc = int(cb.max()) + 1
+            key = slot * nc + cb
+            uk, firstc, kinv = np.unique(key, return_index=True, return_inverse=True)
+            par = uk // nc
+            o = np.lexsort((firstc, par))                           # groups by parent, then by first column
+            stays = np.ones(uk.shape[0], dtype=bool)
+            stays[o[1:]] = par[o[1:]] != par[o[:-1]]                # a parent's first child keeps its slot
+            new_slot = np.empty(uk.shape[0], dtype=np.int64)
+            new_slot[stays] = par[stays]
+            mv = np.flatnonzero(~stays)
+            mv = mv[np.argsort(firstc[mv], kind="stable")]
+            new_slot[mv] = prev + np.arange(mv.shape[0])
+            nb = prev + int(mv.shape[0])
+            parent = np.empty(nb, dtype=np.int64)
+            parent[new_slot] = par
+            rep = np.empty(nb, dtype=np.int64)
+            rep[new_slot] = firstc
+            slot = new_slot[kinv.reshape(-1)]
+            self.parent.append(parent); self.rep.append(rep); self.level_n.append(nb)
+            prev = nb
+        self.col_node = slot
+        self.evals = int(sum(self.level_n))              # block evaluations of the train (the unshared launch: n * depth)
+
+    @staticmethod
+    def codes_from_keep(keep):
+        """keep bool [depth, 2, n] (droppath_keep_host) -> codes [depth, n]: a block's scale depends on its rate and the keep decision only."""
+        k = np.asarray(keep)
+        return (k[:, 0].astype(np.int64) << 1) | k[:, 1].astype(np.int64)
+
+    @staticmethod
+    def codes_from_table(dp):
+        """dp float [depth, 2, n] (a DropPath table read on the host) -> codes [depth, n]: equal codes <=> equal bit patterns of both scales."""
+        a = np.ascontiguousarray(np.asarray(dp, dtype=np.float32)).view(np.uint32).astype(np.uint64)
+        key = (a[:, 0] << np.uint64(32)) | a[:, 1]
+        return np.stack([np.unique(key[b], return_inverse=True)[1].reshape(-1) for b in range(key.shape[0])]).astype(np.int64)
+
+    def node_cols(self):
+        """The columns each node of the last block stands for (list per slot)."""
+        out = [[] for _ in range(self.level_n[-1] if self.level_n else self.U)]
+        for j, s_ in enumerate(self.col_node.tolist()):
+            out[s_].append(j)
+        return out
+
+    def upload(self, device, droppath=None):
+        """The device side of a launch: ONE host-to-device copy (pinned, asynchronous: no synchronisation) of every index table, the nodes'
+        DropPath scales gathered from the train's table ``droppath`` [depth, 2, n] (one launch), and the fork list per block."""
+        segs, offs, nbytes = [], {}, 0
+
+        def add(name, arr):
+            nonlocal nbytes
+            b = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
+            offs[name] = (nbytes, b.shape[0], arr.dtype)
+            segs.append(b)
+            pad = (-b.shape[0]) % 16
+            if pad:
+                segs.append(np.zeros(pad, dtype=np.uint8))
+            nbytes += b.shape[0] + pad
+        add("uimg", self.uimg.astype(np.int32))
+        add("col_node", self.col_node.astype(np.int32))
+        nmax = max(self.level_n) if self.level_n else self.U
+        if droppath is not None:
+            gi = np.zeros((self.depth, 2, nmax), dtype=np.int64)
+            for b in range(self.depth):
+                gi[b, :, :self.level_n[b]] = self.rep[b][None, :]
+            add("gather", gi)
+        prev = self.U
+        for b in range(self.depth):
+            if self.level_n[b] > prev:
+                add("fork%d" % b, self.parent[b][prev:].astype(np.int32))
+            prev = self.level_n[b]
+        host = torch.from_numpy(np.concatenate(segs)).pin_memory()
+        dev = host.to(device, non_blocking=True)
+        td = {"int32": torch.int32, "int64": torch.int64}
+
+        def view(name):
+            o, nb, dt = offs[name]
+            return dev[o:o + nb].view(td[str(dt)])
+        self.uimg_dev, self.col_node_dev = view("uimg"), view("col_node")
+        self.dp = torch.gather(droppath, 2, view("gather").view(self.depth, 2, nmax)) if droppath is not None else None
+        self.forks, prev = [], self.U
+        for b in range(self.depth):
+            nb = self.level_n[b]
+            self.forks.append((view("fork%d" % b), nb - prev, prev) if nb > prev else None)
+            prev = nb
+        self.launched = []                      # the node count of every block the forward launched (tests)
+        return self
+
+
+def _column_kernels(pl, cfg):
+    """Each inference column's launch-size-dependent kernels (nets/vit.py launch_kernels) in the launch train the plan puts it in."""
+    out = {}
+    if pl.x3_cols is not None:
+        ni = len(pl.host_cols["inf"])
+        trains = [("x3", None, "bf16x3"), ("mix", ni, "bf16"), ("rest", None, "bf16")]
+    else:
+        trains = [("inf", None, "bf16"), ("rest", None, "bf16")]
+    for name, kai, prec in trains:
+        cols = pl.host_cols.get(name, [])
+        if cols:
+            k = _vit.launch_kernels(cfg, len(cols), kernels_as_images=kai, precision=prec)
+            out.update((c, k) for c in cols)
+    return out
+
+
+def _plan_for_sharing(default, whole, cfg):
+    """share_pass_prefixes: the plan whose deferred-to-read moves take whole images (more rows shared inside a train) -- but only when every
+    column keeps the kernels it has in the default plan; a move that takes a train across a kernel switch (the fused MLP's launch size, a GEMM
+    tile rule) would change that column's bits, so the default plan's column-wise moves stay then."""
+    return whole if _column_kernels(whole, cfg) == _column_kernels(default, cfg) else default
 
 
 READ_ROWS_PRECISIONS = ("bf16", "bf16x3")
@@ -234,6 +405,31 @@ def grad_rows_precision(args, net_cls=None):
     return v
 
 
+def share_pass_prefixes(args, net_cls=None):
+    """Opt-in (off by default, never the headline): compute the ViT inference rows once across passes whose DropPath draws agree so far (a
+    pass-prefix tree per no-save launch train, _PassTree).  Every logit, feature and result of the step stays the same bit for bit.
+    ``args.share_pass_prefixes``, else the environment variable SR_SHARE_PASS_PREFIXES ("0" / "1"), else off.
+    Raises ValueError for an unparsable value, NotImplementedError when on for a backbone without that forward (``pass_prefix_sharing``):
+    BERT, Wav2Vec2 and HuBERT draw dropout from the embedding on (no two passes share a prefix), WideResNet's BatchNorm couples rows."""
+    v = getattr(args, "share_pass_prefixes", None)
+    if v is None:
+        v = os.environ.get("SR_SHARE_PASS_PREFIXES", "0")
+    if isinstance(v, bool):
+        on = v
+    else:
+        t = str(v).strip().lower()
+        if t in ("1", "true", "yes", "on"):
+            on = True
+        elif t in ("0", "false", "no", "off"):
+            on = False
+        else:
+            raise ValueError("share_pass_prefixes must be 0 / 1 (or true / false), got %r" % (v,))
+    if on and net_cls is not None and not getattr(net_cls, "pass_prefix_sharing", False):
+        raise NotImplementedError("share_pass_prefixes is built for the ViT engine only; backbone %s cannot share rows between passes"
+                                  % getattr(net_cls, "__name__", net_cls))
+    return on
+
+
 class SRConsistencyBase(AlgorithmBase):
     """Shared step of the confidence-threshold SemiReward algorithms (SRFlexMatch, SRFixMatch): the reference classes
     differ only in their MaskingHook and in whether ``train_step`` receives ``idx_ulb``."""
@@ -242,9 +438,11 @@ class SRConsistencyBase(AlgorithmBase):
         # checked before any device work; a builder whose class cannot be told is checked on the built model below
         self.read_rows_precision = read_rows_precision(args, backbone_class(net_builder))
         self.grad_rows_precision = grad_rows_precision(args, backbone_class(net_builder))
+        self.share_pass_prefixes = share_pass_prefixes(args, backbone_class(net_builder))
         super().__init__(args, net_builder, tb_log, logger)
         read_rows_precision(argparse.Namespace(read_rows_precision=self.read_rows_precision), type(self.model))
         grad_rows_precision(argparse.Namespace(grad_rows_precision=self.grad_rows_precision), type(self.model))
+        share_pass_prefixes(argparse.Namespace(share_pass_prefixes=self.share_pass_prefixes), type(self.model))
         if self.grad_rows_precision == "bf16x3":
             self.model.grad_rows_precision = "bf16x3"        # the opt-in of the backbone's saved split-bf16 forward
         self._init_thresholds(args)
@@ -281,6 +479,7 @@ class SRConsistencyBase(AlgorithmBase):
         self._phases = []
         self.inject_droppath = None            # tests: list of [depth,2,Bt] tensors, one per pass
         self.trace = None                      # tests: dict filled with per-pass intermediates when not None
+        self.pass_trees = []                   # share_pass_prefixes: the trees of the latest step's launch trains (tests, profiles)
 
     def _init_thresholds(self, args):
         raise NotImplementedError
@@ -303,20 +502,41 @@ class SRConsistencyBase(AlgorithmBase):
         C, D = self.num_classes, m.cfg.embed_dim
         ng_, ni_ = pl.grad_cols.numel(), pl.inf_cols.numel()
         capturing = torch.cuda.is_current_stream_capturing()      # (a captured step owns its allocations: no record_stream bookkeeping)
+        share = self.share_pass_prefixes
+        # share_pass_prefixes: which columns of a launch train agree on their DropPath draws is known on the HOST without a synchronisation
+        # (codes(name, a): per block, equal codes <=> equal scales; a test-injected table is read back, a sync is fine there)
+        codes = lambda name, a: None                                                                 # noqa: E731
         if droppath_cols is not None:
             dp_all = droppath_cols.to(self.device)                                                   # [depth,2,ncols]
             sel = lambda cols, a: dp_all.index_select(2, cols).contiguous()                          # noqa: E731
+            if share:
+                dp_host = droppath_cols.detach().float().cpu().numpy()
+                codes = lambda name, a: _PassTree.codes_from_table(dp_host[:, :, pl.host_cols[name]])  # noqa: E731
         elif m.training and m.cfg.drop_path_rate > 0:
             if m.droppath_by_cols:
                 # ONE launch: the columns of the draw in launch order; a launch train's table is the slice [a, a + len(cols))
                 dp_all = m.make_droppath(pl.ncols, cols=pl.perm_cols)
                 sel = lambda cols, a: dp_all[:, :, a:a + cols.numel()]                               # noqa: E731
+                if share:
+                    keep = _vit.droppath_keep_host(m.dp_probs_host.numpy(), m.cfg.depth, pl.ncols, m.last_droppath_seed, cols=pl.perm_host)
+                    codes = lambda name, a: _PassTree.codes_from_keep(keep[:, :, a:a + len(pl.host_cols[name])])     # noqa: E731
             else:
                 dp_all = m.make_droppath(pl.ncols)
                 sel = lambda cols, a: dp_all.index_select(2, cols).contiguous()                      # noqa: E731
         else:
             dp_all = None
             sel = lambda cols, a: None                                                               # noqa: E731
+        if share:
+            assert m.scatter_outputs and m.droppath_by_cols and not capturing, "share_pass_prefixes: the ViT engine's eager step"
+            self.pass_trees = []
+
+        def tree_of(name, a):
+            if not share:
+                return None
+            hc = pl.host_cols[name]
+            t_ = _PassTree([pl.cols_img_host[c] for c in hc], codes(name, a), m.cfg.depth)
+            self.pass_trees.append((name, t_))
+            return t_
         scatter = m.scatter_outputs
         logits = torch.empty(pl.ncols, C, dtype=torch.float32, device=self.device)
         feats = torch.empty(pl.ncols, D, dtype=torch.float32, device=self.device)
@@ -336,20 +556,25 @@ class SRConsistencyBase(AlgorithmBase):
             # read_rows_precision = bf16x3: the columns the step reads run the split-bf16 chain; the unread columns _Plan moved into the
             # read launch keep the bf16 kernels the whole launch would have taken (kernels_as_images), in a launch of their own
             nx = pl.x3_cols.numel()
-            chunks = ([(pl.x3_cols, pl.x3_img, ng_, dict(precision="bf16x3"))] if nx else []) + \
-                ([(pl.mix_cols, pl.mix_img, ng_ + nx, dict(buftag="m", kernels_as_images=ni))] if ni > nx else [])
+            chunks = ([(pl.x3_cols, pl.x3_img, ng_, dict(precision="bf16x3"), "x3")] if nx else []) + \
+                ([(pl.mix_cols, pl.mix_img, ng_ + nx, dict(buftag="m", kernels_as_images=ni), "mix")] if ni > nx else [])
         else:
-            chunks = [(pl.inf_cols, pl.inf_img, ng_, {})] if ni else []
+            chunks = [(pl.inf_cols, pl.inf_img, ng_, {}, "inf")] if ni else []
         if side is None and nr:
-            chunks.append((pl.rest_cols, pl.rest_img, ng_ + ni, {}))
-        dps = [sel(cols, a) for cols, _, a, _ in chunks]
+            chunks.append((pl.rest_cols, pl.rest_img, ng_ + ni, {}, "rest"))
+        dps = [sel(cols, a) for cols, _, a, _, _ in chunks]
+        trees = [tree_of(name, a) for _, _, a, _, name in chunks]
         dp_rest = sel(pl.rest_cols, ng_ + ni) if (side is not None and nr) else None
-        chunks = [(cols, imgi, kw) for cols, imgi, _, kw in chunks]
+        tree_rest = tree_of("rest", ng_ + ni) if (side is not None and nr) else None
+        chunks = [(cols, imgi, kw) for cols, imgi, _, kw, _ in chunks]
         if side is not None:
             ready = torch.cuda.Event()
             ready.record(main)                       # parameters, images, DropPath draws are final here
-        for (cols, imgi, kw), dpi in zip(chunks, dps):
-            if scatter:                  # the head writes the rows of the step's tables itself
+        for (cols, imgi, kw), dpi, tr in zip(chunks, dps, trees):
+            if tr is not None:           # share_pass_prefixes: the train's nodes instead of its columns, then the fan-out to the columns
+                tr.upload(self.device, dpi)
+                m.forward_features(imgs, imgi, tr.dp, save=False, out=(logits, feats, cols), tree=tr, **kw)
+            elif scatter:                # the head writes the rows of the step's tables itself
                 m.forward_features(imgs, imgi, dpi, save=False, out=(logits, feats, cols), **kw)
             else:
                 lg, ft, _ = m.forward_features(imgs, imgi, dpi, save=False, **kw)
@@ -376,7 +601,11 @@ class SRConsistencyBase(AlgorithmBase):
                     # Rows whose outputs nothing reads before the step ends (strong / labelled rows of the passes whose loss the
                     # reference discards): 60 % of the forward work, off the critical path.  The masks, losses and the latency-bound
                     # backward of the 16 gradient images (small launches that leave most CUs idle) run on the main stream meanwhile.
-                    if scatter:
+                    if tree_rest is not None:
+                        tree_rest.upload(self.device, dp_rest)
+                        m.forward_features(imgs, pl.rest_img, tree_rest.dp, save=False, buftag="r", out=(logits, feats, pl.rest_cols),
+                                           tree=tree_rest)
+                    elif scatter:
                         m.forward_features(imgs, pl.rest_img, dp_rest, save=False, buftag="r", out=(logits, feats, pl.rest_cols))
                     else:
                         lg_r, ft_r, _ = m.forward_features(imgs, pl.rest_img, dp_rest, save=False, buftag="r")
@@ -467,11 +696,14 @@ class SRConsistencyBase(AlgorithmBase):
         return TokenBatch.cat(batches)
 
     def _make_plan(self, nl, nu, K, defer_fraction=None):
-        return _Plan.cat_passes(nl, nu, K, self.device, extra_pass0_strong=self.fairness_rows and K > 0,
-                                lb_every_pass=bool(self.use_cat), defer_unread=self.defer_unread_rows,
-                                rows_per_col=getattr(self.model.cfg, "num_tokens", None),
-                                elide_unread=self.elide_unread_rows, defer_fraction=defer_fraction,
-                                split_read=self.read_rows_precision == "bf16x3")
+        mk = lambda whole: _Plan.cat_passes(nl, nu, K, self.device, extra_pass0_strong=self.fairness_rows and K > 0,    # noqa: E731
+                                            lb_every_pass=bool(self.use_cat), defer_unread=self.defer_unread_rows,
+                                            rows_per_col=getattr(self.model.cfg, "num_tokens", None),
+                                            elide_unread=self.elide_unread_rows, defer_fraction=defer_fraction,
+                                            split_read=self.read_rows_precision == "bf16x3", whole_images=whole)
+        if self.share_pass_prefixes:
+            return _plan_for_sharing(mk(False), mk(True), self.model.cfg)
+        return mk(False)
 
     def _forward_passes(self, imgs, nl, nu, K):
         key = (nl, nu, K, bool(self.use_cat), self.elide_unread_rows)

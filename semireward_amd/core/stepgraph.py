@@ -81,7 +81,11 @@ class StepScalars:
 
 class StepGraph:
     """``step(**batch)`` == ``train_step(**batch)`` + ``ParamUpdateHook.after_train_step`` of the algorithm, eagerly for the first ``warm`` steps of
-    a variant (and while the step schedule is still being tuned), from then on as a captured HIP graph."""
+    a variant (and while the step schedule is still being tuned), from then on as a captured HIP graph.
+
+    With ``share_pass_prefixes`` on, every step runs eagerly and none is captured: the pass-prefix trees of the step's inference launch trains
+    follow that step's DropPath draws, so their launch shapes (node counts per block, forks) change from step to step and a captured graph
+    would replay the wrong ones."""
 
     MAX_GRAPHS = 8           # captured variants kept (least recently used one dropped beyond that)
     COUNTERS = (("optimizer", "step_count"), ("optimizer", "sched_step"), ("model", "_rng_calls"), ("rewarder_optimizer", "steps"))
@@ -154,7 +158,8 @@ class StepGraph:
             return out, alg.log_dict
         n = self.seen.get(key, 0)
         self.seen[key] = n + 1
-        if n < self.warm or getattr(alg, "_tuners", None) or getattr(alg, "_untuned", None) or alg.trace is not None or split is None:
+        if n < self.warm or getattr(alg, "_tuners", None) or getattr(alg, "_untuned", None) or alg.trace is not None or split is None or \
+                getattr(alg, "share_pass_prefixes", False):
             self.eager_steps += 1
             return self._eager(batch)
         # ---- capture this step (nothing executes during capture), then replay it once: that IS this step

@@ -1200,7 +1200,7 @@ extern "C" int srhip_gemm_nt_plan(int epilogue, int M, int N, int K, float beta)
 static int gemm_nt_impl(int epilogue, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
                         int M, int N, int K, const float* bias, const float* row_scale, int rows_per_sample,
                         const void* aux_in, void* aux_out, int ldaux, float alpha, float beta, uint32_t drop_key, uint32_t drop_thresh,
-                        float drop_scale, void* stream, const float* const* ln = nullptr) {
+                        float drop_scale, void* stream, const float* const* ln = nullptr, int plan_M = 0) {
   if (M <= 0 || N <= 0 || K <= 0 || (K % BK) || (N % 4) || (lda % 8) || (ldb % 8) || (ldc % 4)) return SR_EINVAL;   // BK = 32
   if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return SR_EINVAL;
   if (epilogue == SRHIP_EPI_DGELU_BF16 && !aux_in) return SR_EINVAL;
@@ -1221,7 +1221,9 @@ static int gemm_nt_impl(int epilogue, const void* A, int lda, const void* B, int
   const int grid = cdiv(M, BM) * cdiv(N, BN);
   hipStream_t s = (hipStream_t)stream;
   int splits = 1;
-  int plan = gemm_plan(epilogue, M, N, K, beta, &splits);
+  // plan_M > 0 (srhip_gemm_nt_planned): the kernel is the one a launch of plan_M rows would take -- rows split off a larger launch keep its
+  // tile kernel, hence its per-row arithmetic, bit for bit
+  int plan = gemm_plan(epilogue, plan_M > 0 ? plan_M : M, N, K, beta, &splits);
   // the residual that owes its LayerNorm exists for the 64 x 64, 128 x 128 and two-wave-group kernels: where the plan says a lockstep 256-row
   // kernel (operands past 2 GiB, or a pinned test mode) it takes the 128 x 128 tiles instead
   if (ln && (plan == SRHIP_GEMM_PLAN_BIG256 || plan == SRHIP_GEMM_PLAN_BIG128 || plan == SRHIP_GEMM_PLAN_BIG2WG ||
@@ -1293,6 +1295,16 @@ extern "C" int srhip_gemm_nt(int epilogue, const void* A, int lda, const void* B
                              const void* aux_in, void* aux_out, int ldaux, float alpha, float beta, void* stream) {
   return gemm_nt_impl(epilogue, A, lda, B, ldb, C, ldc, M, N, K, bias, row_scale, rows_per_sample, aux_in, aux_out, ldaux, alpha, beta, 0u, 0u,
                       1.0f, stream);
+}
+
+extern "C" int srhip_gemm_nt_planned(int epilogue, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
+                                     int M, int N, int K, const float* bias, const float* row_scale, int rows_per_sample,
+                                     const void* aux_in, void* aux_out, int ldaux, float alpha, float beta, int plan_M, void* stream) {
+  if (plan_M < M) return SR_EINVAL;
+  // a split-K plan accumulates with atomics in an order no row count pins: refused rather than silently different
+  if (epilogue == SRHIP_EPI_F32 && beta == 1.0f) return SR_EINVAL;
+  return gemm_nt_impl(epilogue, A, lda, B, ldb, C, ldc, M, N, K, bias, row_scale, rows_per_sample, aux_in, aux_out, ldaux, alpha, beta, 0u, 0u,
+                      1.0f, stream, nullptr, plan_M);
 }
 
 extern "C" int srhip_gemm_nt_dropout(int epilogue, const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,

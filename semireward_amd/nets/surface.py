@@ -19,6 +19,7 @@ class ModuleSurface:
     droppath_by_cols = False    # make_droppath(cols=...) lays the DropPath table out in the caller's column order (no index_select)
     precise_rows = False        # forward_features(precision="bf16x3"): split-bf16 products, fp32 activations (read_rows_precision)
     precise_grad_rows = False   # forward_features(save=True, precision="bf16x3") and its backward (grad_rows_precision)
+    pass_prefix_sharing = False  # forward_features(tree=...): passes whose DropPath draws agree so far share rows (share_pass_prefixes)
     couples_batch_rows = False  # BatchNorm: every forward call is its own statistics group (no cross-pass batching)
     takes_tokens = False        # inputs are token batches (dicts of input_ids / attention_mask), not image tensors
     lazy_transposed = False     # after an optimizer step the transposed copies are only marked stale (ensure_transposed)

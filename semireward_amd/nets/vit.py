@@ -17,6 +17,7 @@ Data layout in HBM (B images, N tokens, D channels, M = B*N rows):
 import math
 import types
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -71,6 +72,55 @@ _FUSED_NEXT_LN = True      # ... which then also writes the next block's norm1 o
 _FUSED_MLP_MIN_ROWS = 16384
 
 
+def _fused_mlp(cfg, rows):
+    """Whether a no-save launch whose kernel choice is made for ``rows`` rows takes the fused row-streaming MLP (forward_features)."""
+    Hd = cfg.hidden
+    return cfg.embed_dim == 384 and Hd % 128 == 0 and Hd <= 4096 and rows >= _FUSED_MLP_MIN_ROWS and _FUSED_MLP
+
+
+def launch_kernels(cfg, n_images, kernels_as_images=None, precision="bf16"):
+    """The launch-size-dependent kernel choices of a no-save forward_features over ``n_images`` images (host logic, no launch): two launches
+    with equal results here run every row through the same kernels, hence to the same bits.  bf16x3: fixed tiles, nothing depends on the size.
+    bf16: the fused / unfused MLP switch and the tile kernel (srhip_gemm_nt_plan at the current run-time settings) of every GEMM launched."""
+    if precision == "bf16x3":
+        return ("bf16x3",)
+    D, N, H, Hd = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden
+    M = n_images * N
+    fused = _fused_mlp(cfg, max(M, (kernels_as_images or 0) * N))
+    fused_attn = _FUSED_ATTN and ops.attn_block_supported(N, D, H)
+    gemms = []
+    if cfg.in_chans * cfg.patch_size ** 2 > 64:
+        gemms.append((ops.EPI_F32, n_images * (N - 1), D, cfg.in_chans * cfg.patch_size ** 2))
+    if not fused_attn:
+        gemms.append((ops.EPI_BF16, M, 3 * D, D))
+    if not (fused and _FUSED_PROJ):
+        gemms.append((ops.EPI_RESID_F32, M, D, D))
+    if not fused:
+        gemms += [(ops.EPI_GELU_BF16, M, Hd, D), (ops.EPI_RESID_F32, M, D, Hd)]
+    return (fused, fused_attn) + tuple(ops.gemm_nt_plan(e, m, n, k) for e, m, n, k in gemms)
+
+
+def droppath_keep_host(probs, depth, B, seed, cols=None):
+    """Host replica of droppath_fill_kernel (csrc/vit_ops.hip): which samples KEEP each block's two branches in the draw of ``seed`` over B columns
+    -- bool [depth, 2, B], or [depth, 2, len(cols)] for the columns ``cols`` in that order -- bit for bit the device table's ``!= 0``, with no
+    device round trip.  probs: the fp32 per-block drop rates as a host array (the values the device table was made from).
+    The kernel: i = (2 * block + branch) * B + col, splitmix64 of seed + 0x9E3779B97F4A7C15 * (i + 1), u = (z >> 40) * 2^-24, keep iff
+    p <= 0 or u < 1.0f - p in fp32."""
+    p = np.asarray(probs, dtype=np.float32)[:depth]
+    col = np.arange(B, dtype=np.int64) if cols is None else np.asarray(cols, dtype=np.int64)
+    col = np.where((col < 0) | (col >= B), 0, col)
+    i = (np.arange(2 * depth, dtype=np.int64)[:, None] * B + col[None, :]).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        z = np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) + np.uint64(0x9E3779B97F4A7C15) * (i + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    u = (z >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)      # exact: < 2^24 times a power of two
+    pp = np.repeat(p, 2)[:, None]
+    keep = (pp <= np.float32(0)) | (u < (np.float32(1.0) - pp))
+    return keep.reshape(depth, 2, col.shape[0])
+
+
 class FwdContext:
     """Activations kept by a ``save=True`` forward for the hand-written backward."""
     __slots__ = ("B", "img", "img_index", "dp", "xs", "xmid", "ln1", "ln2", "qkv", "ao", "lse", "pre", "h", "st1", "st2",
@@ -84,6 +134,7 @@ class VisionTransformer(ModuleSurface):
     droppath_by_cols = True       # make_droppath(cols=...) lays the DropPath table out in the caller's column order (no index_select)
     precise_rows = True           # forward_features(precision="bf16x3"): split-bf16 products, fp32 activations (read_rows_precision)
     precise_grad_rows = True      # forward_features(save=True, precision="bf16x3") + its backward (grad_rows_precision)
+    pass_prefix_sharing = True    # forward_features(tree=...): passes that agree on their DropPath draws so far share rows (share_pass_prefixes)
     lazy_transposed = True        # the optimizer only marks the transposed weight copies stale (ensure_transposed)
 
     def __init__(self, cfg=None, device="cuda", **kw):
@@ -101,7 +152,9 @@ class VisionTransformer(ModuleSurface):
                 n = "blocks.%d.%s" % (i, w)
                 r, c = self.offsets[n][1]
                 self.wT[n] = torch.zeros(c, r, dtype=torch.bfloat16, device=self.device)
-        self.dp_probs = torch.linspace(0, cfg.drop_path_rate, cfg.depth).to(self.device)    # vit.py:247-249
+        self.dp_probs_host = torch.linspace(0, cfg.drop_path_rate, cfg.depth)                # vit.py:247-249
+        self.dp_probs = self.dp_probs_host.to(self.device)
+        self.last_droppath_seed = None       # 64-bit seed of the latest make_droppath draw (droppath_keep_host replays its decisions)
         self._rng_calls = 0
         self.seed = 0
 
@@ -138,6 +191,9 @@ class VisionTransformer(ModuleSurface):
         that order ([depth, 2, len(cols)])."""
         dp = torch.empty(self.cfg.depth, 2, B if cols is None else cols.numel(), dtype=torch.float32, device=self.device)
         self._rng_calls += 1
+        # (under core/stepgraph.py the device seed below is the pushed (seed << 32) + counter at the step start plus the draw number inside the
+        # step: the same value)
+        self.last_droppath_seed = ((self.seed << 32) + self._rng_calls) & 0xFFFFFFFFFFFFFFFF
         sc = getattr(self, "step_scalars", None)
         if sc is not None:
             # core/stepgraph.py: the step's seed base ((seed << 32) + the draw counter at the start of the step) sits in device memory; this call
@@ -199,24 +255,33 @@ class VisionTransformer(ModuleSurface):
 
     # ---- forward ----------------------------------------------------------------------------------
     def forward_features(self, img, img_index=None, droppath=None, save=False, B=None, buftag="", out=None, precision="bf16",
-                         kernels_as_images=None):
+                         kernels_as_images=None, tree=None):
         """img fp32 [n_img, C, H, W]; img_index int32 [B] (optional gather); droppath fp32 [depth,2,B] or None.
         Returns (logits [B,C], feat [B,D], ctx or None).
         precision="bf16x3": the split-bf16 chain of _forward_x3 instead of the bf16-operand one; with save=True the context keeps fp32
         activations for the split-bf16 backward (grad_rows_precision).
-        kernels_as_images: pick the kernels a launch of that many images would take (rows split off a larger launch keep its results bit for bit)."""
+        kernels_as_images: pick the kernels a launch of that many images would take (rows split off a larger launch keep its results bit for bit).
+        tree (share_pass_prefixes, rows without a backward, out= required): a pass-prefix tree of the B columns (algorithms/srflexmatch.py
+        _PassTree, uploaded): the patch embedding runs once per distinct image (tree.uimg_dev), block i over the tree.level_n[i] nodes of that
+        block (their DropPath scales: droppath = tree.dp, [depth, 2, >= max nodes]), new nodes are forked from their parents in front of the
+        block (srhip_vit_fork), and every column takes its node's outputs at its row of ``out`` (srhip_vit_fanout).  Every kernel choice is
+        made for the unshared launch of B images, so each column's logits and feature are that launch's, bit for bit."""
+        if tree is not None:
+            assert not save and out is not None, "a pass-prefix tree is for rows without a backward that write the step's tables"
         if precision == "bf16x3":
             if save:
                 assert self.grad_rows_precision == "bf16x3", "a bf16x3 forward with saved activations needs model.grad_rows_precision = 'bf16x3'"
                 return self._forward_x3_save(img, img_index, droppath, B, out)
-            return self._forward_x3(img, img_index, droppath, B, buftag, out)
+            return self._forward_x3(img, img_index, droppath, B, buftag, out, tree)
         if precision != "bf16":
             raise ValueError("precision must be 'bf16' or 'bf16x3', got %r" % (precision,))
         cfg = self.cfg
         D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
-        B = int(img_index.numel()) if img_index is not None else (B or img.shape[0])
+        B = tree.n if tree is not None else (int(img_index.numel()) if img_index is not None else (B or img.shape[0]))
         M = B * N
         Mk = max(M, (kernels_as_images or 0) * N)       # the launch size the kernel choice is made for
+        # a tree launches fewer rows per block than the unshared launch: its GEMMs take that launch's tile kernel (srhip_gemm_nt_planned)
+        gp = dict(plan_M=M) if tree is not None else {}
         f32, bf16 = torch.float32, torch.bfloat16
         tag = ("s" if save else "i") + buftag        # buftag: a second inference launch train on another stream needs its own workspaces
         ctx = None
@@ -230,28 +295,37 @@ class VisionTransformer(ModuleSurface):
             qkv = self._buf(tag + "qkv", (M, 3 * D), bf16)
             ao = self._buf(tag + "ao", (M, D), bf16)
         # rows without a backward run LN2 + fc1 + GELU + fc2 + residual as ONE kernel (ViT-S width; SRHIP_FUSED_MLP=0: off)
-        fused_mlp = (not save) and D == 384 and Hd % 128 == 0 and Hd <= 4096 and Mk >= _FUSED_MLP_MIN_ROWS and _FUSED_MLP
+        fused_mlp = (not save) and _fused_mlp(cfg, Mk)
         hbuf = None if (fused_mlp or save) else self._buf(tag + "h", (M, Hd), bf16)
         fused_attn = (not save) and _FUSED_ATTN and ops.attn_block_supported(N, D, H)       # SRHIP_FUSED_ATTN=0: separate qkv GEMM + attention
         qkvx = self._buf(tag + "qkvx", (B, 3 * D), bf16) if (fused_attn and N == 257) else None
         wb = self.flat_bf16
         P = self.p
         Kp = cfg.in_chans * cfg.patch_size ** 2
+        Be, idx_e = (tree.U, tree.uimg_dev) if tree is not None else (B, img_index)       # the images the patch embedding runs on
         if Kp <= 64:                                # CIFAR-style 2x2 / 4x4 patches: direct fp32 kernel
-            ops.patch_embed_fwd(img, img_index, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("cls_token"),
-                                P("pos_embed"), x, B, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
+            ops.patch_embed_fwd(img, idx_e, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("cls_token"),
+                                P("pos_embed"), x, Be, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
         else:                                       # ViT-S/16 at 224: unfold (bf16) -> GEMM with the [D, 768] filter -> + bias / pos / cls
             Np = N - 1
             col = self._buf(tag + "col", (B * Np, Kp), bf16)
             tok = self._buf(tag + "tok", (B * Np, D), f32)
-            ops.patch_im2col(img, img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
-            ops.gemm_nt(ops.EPI_F32, col, P("patch_embed.proj.weight", wb), tok, B * Np, D, Kp)
-            ops.patch_assemble(tok, P("patch_embed.proj.bias"), P("cls_token"), P("pos_embed"), x, B, Np, D)
+            ops.patch_im2col(img, idx_e, col, Be, cfg.in_chans, cfg.img_size, cfg.patch_size)
+            ops.gemm_nt(ops.EPI_F32, col, P("patch_embed.proj.weight", wb), tok, Be * Np, D, Kp, **(dict(plan_M=B * Np) if tree is not None else {}))
+            ops.patch_assemble(tok, P("patch_embed.proj.bias"), P("cls_token"), P("pos_embed"), x, Be, Np, D)
         scale = 64 ** -0.5
         dst0, dst1 = (droppath.stride(0), droppath.stride(1)) if droppath is not None else (0, 0)      # (a column range of the step's table: strided rows)
         ln_ready = False           # the previous block's fused launch already wrote this block's norm1 output
         for i in range(cfg.depth):
             b = "blocks.%d." % i
+            if tree is not None:
+                # this block's nodes: the new ones start as copies of their parents (x, and the norm1 output when the last launch wrote it)
+                fk = tree.forks[i]
+                if fk is not None:
+                    ops.vit_fork(x, ln if ln_ready else None, fk[0], fk[1], fk[2], N, D)
+                B = tree.level_n[i]
+                M = B * N
+                tree.launched.append(B)
             s1 = ops.RawRows(droppath, i * dst0) if droppath is not None else None            # droppath[i, 0], droppath[i, 1] without building views
             s2 = ops.RawRows(droppath, i * dst0 + dst1) if droppath is not None else None
             if save:
@@ -267,7 +341,7 @@ class VisionTransformer(ModuleSurface):
                 ops.attn_block_fused(ln, P(b + "attn.qkv.weight", wb), P(b + "attn.qkv.bias"), ao, B, N, D, H, scale, qkv_extra=qkvx,
                                      out_scale=s1 if ao_scaled else None)
             else:
-                ops.gemm_nt(ops.EPI_BF16, ln, P(b + "attn.qkv.weight", wb), qkv, M, 3 * D, D, bias=P(b + "attn.qkv.bias"))
+                ops.gemm_nt(ops.EPI_BF16, ln, P(b + "attn.qkv.weight", wb), qkv, M, 3 * D, D, bias=P(b + "attn.qkv.bias"), **gp)
                 ops.attn_fwd(qkv, ao, ctx.lse[i] if save else None, B, N, H, scale)
             if save:
                 xm = ctx.xmid[i]
@@ -293,15 +367,17 @@ class VisionTransformer(ModuleSurface):
                                    next_beta=P(nb + "norm1.bias") if ln_ready else None, ao_scaled=ao_scaled)
             else:
                 ops.gemm_nt(ops.EPI_RESID_F32, ao, P(b + "attn.proj.weight", wb), x, M, D, D, bias=P(b + "attn.proj.bias"),
-                            row_scale=s1, rows_per_sample=N)
+                            row_scale=s1, rows_per_sample=N, **gp)
                 if fused_mlp:
                     ops.mlp_fused(x, P(b + "norm2.weight"), P(b + "norm2.bias"), cfg.eps, P(b + "mlp.fc1.weight", wb),
                                   P(b + "mlp.fc1.bias"), P(b + "mlp.fc2.weight", wb), P(b + "mlp.fc2.bias"), s2, N, M, D, Hd)
                 else:
                     ops.layernorm_fwd(x, P(b + "norm2.weight"), P(b + "norm2.bias"), cfg.eps, ln, None, None, M, D)
-                    ops.gemm_nt(ops.EPI_GELU_BF16, ln, P(b + "mlp.fc1.weight", wb), hbuf, M, Hd, D, bias=P(b + "mlp.fc1.bias"))
+                    ops.gemm_nt(ops.EPI_GELU_BF16, ln, P(b + "mlp.fc1.weight", wb), hbuf, M, Hd, D, bias=P(b + "mlp.fc1.bias"), **gp)
                     ops.gemm_nt(ops.EPI_RESID_F32, hbuf, P(b + "mlp.fc2.weight", wb), x, M, D, Hd, bias=P(b + "mlp.fc2.bias"),
-                                row_scale=s2, rows_per_sample=N)
+                                row_scale=s2, rows_per_sample=N, **gp)
+        if tree is not None:
+            return self._tree_head(x, tree, out, tag, B)
         if out is not None:
             # out = (logits_all, feats_all, rows): the head writes image b's outputs to row rows[b] of the caller's buffers (the step's
             # [(pass, image), .] tables) -- no index_copy_ launches behind this forward; the dense feat is only kept for a backward
@@ -321,13 +397,26 @@ class VisionTransformer(ModuleSurface):
                          ctx.xhat if save else None, ctx.rstd if save else None, B, N, D, C)
         return logits, feat, ctx
 
-    def _forward_x3(self, img, img_index, droppath, B, buftag, out):
+    def _tree_head(self, x, tree, out, tag, n_nodes):
+        """Head of a pass-prefix tree forward: final norm + head over the last block's nodes into dense node tables, then every column's row of
+        the step's tables takes its node's outputs (the same head kernel and values as the unshared launch's scatter head)."""
+        cfg = self.cfg
+        D, N, C = cfg.embed_dim, cfg.num_tokens, cfg.num_classes
+        P = self.p
+        logits_all, feats_all, rows = out
+        feat = self._buf(tag + "tfeat", (tree.n, D), torch.float32)
+        logits = self._buf(tag + "tlogits", (tree.n, C), torch.float32)
+        ops.cls_head_fwd(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, None, None, n_nodes, N, D, C)
+        ops.vit_fanout(logits, feat, n_nodes, tree.col_node_dev, rows, tree.n, logits_all, feats_all, C, D)
+        return None, None, None
+
+    def _forward_x3(self, img, img_index, droppath, B, buftag, out, tree=None):
         """Inference rows in split-bf16 precision (read_rows_precision = bf16x3): every product is hi.hi + hi.lo + lo.hi of the bf16 planes of
         its fp32 operands (csrc/precise.hip), activations stay fp32, LayerNorm / softmax / GELU / residual / head in fp32 in the order of
         vit.py.  The weights are read from the fp32 parameter block.  Own workspaces (tag "p"): the bf16 chain's buffers are not touched."""
         cfg = self.cfg
         D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
-        B = int(img_index.numel()) if img_index is not None else (B or img.shape[0])
+        B = tree.n if tree is not None else (int(img_index.numel()) if img_index is not None else (B or img.shape[0]))
         M = B * N
         f32 = torch.float32
         tag = "p" + buftag
@@ -338,20 +427,28 @@ class VisionTransformer(ModuleSurface):
         qkv, hbuf = wide[:M * 3 * D].view(M, 3 * D), wide[:M * Hd].view(M, Hd)
         P = self.p
         Kp = cfg.in_chans * cfg.patch_size ** 2
+        Be, idx_e = (tree.U, tree.uimg_dev) if tree is not None else (B, img_index)       # (the x3 tile kernels are fixed: no plan to pin)
         if Kp <= 64:                                # CIFAR-style patches: the direct kernel is fp32 already
-            ops.patch_embed_fwd(img, img_index, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("cls_token"),
-                                P("pos_embed"), x, B, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
+            ops.patch_embed_fwd(img, idx_e, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("cls_token"),
+                                P("pos_embed"), x, Be, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
         else:                                       # ViT-S/16 at 224: fp32 unfold -> bf16x3 GEMM with the fp32 filter -> + bias / pos / cls
             Np = N - 1
             col = self._buf(tag + "col", (B * Np, Kp), f32)
             tok = self._buf(tag + "tok", (B * Np, D), f32)
-            ops.patch_im2col_f32(img, img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
-            ops.gemm_nt_x3(ops.X3_EPI_F32, col, P("patch_embed.proj.weight"), tok, B * Np, D, Kp)
-            ops.patch_assemble(tok, P("patch_embed.proj.bias"), P("cls_token"), P("pos_embed"), x, B, Np, D)
+            ops.patch_im2col_f32(img, idx_e, col, Be, cfg.in_chans, cfg.img_size, cfg.patch_size)
+            ops.gemm_nt_x3(ops.X3_EPI_F32, col, P("patch_embed.proj.weight"), tok, Be * Np, D, Kp)
+            ops.patch_assemble(tok, P("patch_embed.proj.bias"), P("cls_token"), P("pos_embed"), x, Be, Np, D)
         scale = 64 ** -0.5
         dst0, dst1 = (droppath.stride(0), droppath.stride(1)) if droppath is not None else (0, 0)
         for i in range(cfg.depth):
             b = "blocks.%d." % i
+            if tree is not None:
+                fk = tree.forks[i]
+                if fk is not None:
+                    ops.vit_fork(x, None, fk[0], fk[1], fk[2], N, D)
+                B = tree.level_n[i]
+                M = B * N
+                tree.launched.append(B)
             s1 = ops.RawRows(droppath, i * dst0) if droppath is not None else None
             s2 = ops.RawRows(droppath, i * dst0 + dst1) if droppath is not None else None
             ops.layernorm_fwd_f32(x, P(b + "norm1.weight"), P(b + "norm1.bias"), cfg.eps, ln, None, None, M, D)
@@ -363,6 +460,8 @@ class VisionTransformer(ModuleSurface):
             ops.gemm_nt_x3(ops.X3_EPI_GELU_F32, ln, P(b + "mlp.fc1.weight"), hbuf, M, Hd, D, bias=P(b + "mlp.fc1.bias"))
             ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, hbuf, P(b + "mlp.fc2.weight"), x, M, D, Hd, bias=P(b + "mlp.fc2.bias"),
                            row_scale=s2, rows_per_sample=N)
+        if tree is not None:
+            return self._tree_head(x, tree, out, tag, B)
         if out is not None:
             logits_all, feats_all, rows = out
             ops.cls_head_fwd_scatter(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), None, None, None, None,

@@ -215,8 +215,18 @@ def disable_gemm_profile():
 
 # ---- dense ------------------------------------------------------------------------------------
 def gemm_nt(epi, A, B, C, M, N, K, *, lda=None, ldb=None, ldc=None, bias=None, row_scale=None, rows_per_sample=0,
-            aux_in=None, aux_out=None, ldaux=0, alpha=1.0, beta=0.0):
-    """C[M,N] (+)= A[M,K] . B[N,K]^T  (bf16 operands; see srhip_gemm_nt)."""
+            aux_in=None, aux_out=None, ldaux=0, alpha=1.0, beta=0.0, plan_M=None):
+    """C[M,N] (+)= A[M,K] . B[N,K]^T  (bf16 operands; see srhip_gemm_nt).
+    plan_M: take the tile kernel of a launch of plan_M >= M rows (srhip_gemm_nt_planned: the rows keep that launch's results bit for bit)."""
+    if plan_M is not None:
+        args = (epi, _p(A), lda or K, _p(B), ldb or K, _p(C), ldc or N, M, N, K, _p(bias), _p(row_scale), rows_per_sample, _p(aux_in),
+                _p(aux_out), ldaux, alpha, beta, int(plan_M), _s())
+        if _PROFILE is not None:           # (the kernel is the one of a plan_M-row launch)
+            _PROFILE.timed("srhip_gemm_nt_planned", args, 2.0 * M * N * K, _GemmProfile.kernel_name(epi, int(plan_M), N, K),
+                           _GemmProfile.gemm_bytes(epi, M, N, K, aux_in, aux_out, beta))
+            return
+        _call("srhip_gemm_nt_planned", *args)
+        return
     if _PROFILE is not None:
         _PROFILE.timed("srhip_gemm_nt", (epi, _p(A), lda or K, _p(B), ldb or K, _p(C), ldc or N, M, N, K, _p(bias), _p(row_scale),
               rows_per_sample, _p(aux_in), _p(aux_out), ldaux, alpha, beta, _s(),), 2.0 * M * N * K, _GemmProfile.kernel_name(epi, M, N, K),
@@ -725,6 +735,18 @@ def droppath_fill(out, probs, depth, B, seed, cols=None, seed_dev=None):
         _call("srhip_droppath_fill", _p(out), _p(probs), depth, B, seed, _s())
     else:
         _call("srhip_droppath_fill_cols", _p(out), _p(probs), _p(cols), depth, B, cols.numel(), seed, _s())
+
+
+def vit_fork(x, ln, parent, n_new, dst0, rows_per_node, D):
+    """Nodes dst0 .. dst0 + n_new - 1 of a pass-prefix tree level become copies of their parents (int32 device indices, each < dst0): the
+    fp32 residual x [*, rows_per_node, D] and, if given, the bf16 norm1 output ln (srhip_vit_fork, in place)."""
+    _call("srhip_vit_fork", _p(x), _p(ln), _p(parent), n_new, dst0, rows_per_node, D, _s())
+
+
+def vit_fanout(node_logits, node_feat, n_nodes, col_node, col_rows, n_cols, logits_all, feat_all, C, D):
+    """logits_all[col_rows[g]] = node_logits[col_node[g]], feat_all[col_rows[g]] = node_feat[col_node[g]] for g < n_cols (srhip_vit_fanout)."""
+    _call("srhip_vit_fanout", _p(node_logits), _p(node_feat), n_nodes, _p(col_node), _p(col_rows), n_cols, _p(logits_all), _p(feat_all),
+          logits_all.shape[0], C, D, _s())
 
 
 # ---- score filter -----------------------------------------------------------------------------
