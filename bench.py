@@ -18,10 +18,12 @@ Prints ONE JSON line on rank 0 (contract in the task statement).  Exactly ``--st
 regions, each bracketed by barrier + synchronize (all of them are listed in ``repeats``); ``ms_per_step`` is their total time / ``--steps``
 and ``value`` the images per second of that.  ``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy
 (dump_outputs; the inputs and the weights are seeded, and that last step runs from the seeded state of the leg, so that runs and builds
-compare array for array).  Besides ``roofline`` and
-``cpu_baseline`` the line carries ``also``: short legs of the other workloads BASELINE.json's north_star names (ViT-S/16 on 224x224x3, a
-scaled per-GPU batch, the pre-start_timing regime K = 0: each with its own ms_per_step and dominant-kernel roofline; the usb_nlp BERT-base
-and usb_audio Wav2Vec2-base + FreeMatch steps of configs[3] / [4] under their own metric names).
+compare array for array).  That is all a plain run does.
+
+``--full`` adds what the headline figure does not need, after it is measured: ``roofline`` (an instrumented pass of the same steps),
+``cpu_baseline`` and ``also``: short legs of the other workloads BASELINE.json's north_star names (ViT-S/16 on 224x224x3, a scaled per-GPU
+batch, the pre-start_timing regime K = 0: each with its own ms_per_step and dominant-kernel roofline; the usb_nlp BERT-base and usb_audio
+Wav2Vec2-base + FreeMatch steps of configs[3] / [4] under their own metric names), and with data parallel ``grad_exchange_legs``.
 """
 import argparse
 import json
@@ -129,14 +131,18 @@ def parse_args(argv=None):
                     help="N = 1: the data-parallel path with ONE rank on a 1-rank nccl (RCCL) communicator -- every collective of the step is issued "
                          "(gradient exchange selected by the start-up tuner, rccl_ranks: 1, allreduce_ms_per_step in the line); what a one-GPU box can "
                          "show of configs[2]'s backend")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-allreduce-ab", action="store_true", help="N > 1: skip the pinned legs of the gradient exchange (allreduce / overlap / rs_ag ...)")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary legs (224x224, scaled batch, K = 0 regime, BERT, Wav2Vec2)")
-    ap.add_argument("--legs", default="", help="comma-separated subset of the secondary legs (default: all of them)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what its figure does not need: the roofline pass, the secondary legs, the pinned "
+                         "gradient-exchange legs (data parallel) and the CPU baselines; the --no-* options below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline pass")
+    ap.add_argument("--no-allreduce-ab", action="store_true",
+                    help="--full, N > 1: skip the pinned legs of the gradient exchange (allreduce / overlap / rs_ag ...)")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the secondary legs (224x224, scaled batch, K = 0 regime, BERT, Wav2Vec2)")
+    ap.add_argument("--legs", default="", help="--full: comma-separated subset of the secondary legs (default: all of them)")
     ap.add_argument("--extra-budget", type=float, default=900.0,
-                    help="seconds the phases AFTER the headline (secondary legs, gradient-exchange legs, CPU baseline) may take before the line is "
-                         "printed with what is complete")
+                    help="--full: seconds the phases AFTER the headline (secondary legs, gradient-exchange legs, CPU baseline) may take before the "
+                         "line is printed with what is complete")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the headline's last timed step computed (loss, features, logged scalars, the "
                          "updated parameters; a seeded sample of a block past %d elements) as DIR/<name>.npy in float32 / float64, at most %d MB; "
@@ -690,7 +696,7 @@ def worker(a):
                 print("bench.py: %s" % ctx["backend_note"], file=sys.stderr)
 
     head = Leg(a, ctx, net=a.net, img=a.img, bu=a.bu, bl=a.bl, regime=a.regime, alg=a.alg, elide=a.elide_unread_rows)
-    out = head.run(a.steps, a.warmup, max(1, a.repeats), roofline=not a.no_roofline, dump=a.dump_outputs)
+    out = head.run(a.steps, a.warmup, max(1, a.repeats), roofline=a.full and not a.no_roofline, dump=a.dump_outputs)
     if rank == 0 and os.environ.get("SR_PHASES", "0") != "0":
         print("phases (ms since step start: gpu, host):", {k: (round(v[0], 2), round(v[1], 2)) for k, v in head.alg.phase_report().items()},
               file=sys.stderr)
@@ -698,9 +704,9 @@ def worker(a):
         and not a.elide_unread_rows
     del head
     torch.cuda.empty_cache()
-    # The headline is measured.  What follows (secondary legs, the gradient-exchange A/B for N > 1) must never cost the line: if those phases
-    # do not finish within --extra-budget seconds (a collective one rank never reaches does not raise, it waits), every rank's watchdog
-    # ends its process and rank 0 prints the line with what is complete.
+    # The headline is measured; a plain run prints it now.  What --full adds (secondary legs, the gradient-exchange A/B for N > 1, the CPU
+    # baselines) must never cost the line: if those phases do not finish within --extra-budget seconds (a collective one rank never reaches
+    # does not raise, it waits), every rank's watchdog ends its process and rank 0 prints the line with what is complete.
     import threading
     budget = float(a.extra_budget)
     state = {"phase": "secondary legs", "done": False}
@@ -715,8 +721,9 @@ def worker(a):
         os._exit(0)
     watchdog = threading.Timer(budget, _give_up)
     watchdog.daemon = True
-    watchdog.start()
-    if default_headline and not a.no_also:
+    if a.full:
+        watchdog.start()
+    if a.full and default_headline and not a.no_also:
         # the other workloads north_star names, short legs in the same process: fewer steps, one timed region each
         also = out["also"] = []                          # (filled in place: a truncated line carries the legs that finished)
         # (BASELINE.json configs[3] and [4] -- the usb_nlp BERT-base and usb_audio Wav2Vec2-base + FreeMatch steps -- ride along with their own
@@ -768,7 +775,7 @@ def worker(a):
             del leg
             torch.cuda.empty_cache()
     state["phase"] = "gradient-exchange A/B"
-    if (world > 1 or ctx["force_dp"]) and default_headline and not a.no_allreduce_ab:
+    if a.full and (world > 1 or ctx["force_dp"]) and default_headline and not a.no_allreduce_ab:
         # Every gradient exchange pinned once in the SAME run, beside the headline's start-up selection (distributed.ExchangeTuner): the evidence
         # table for the first run on RCCL over xGMI
         ab = out["grad_exchange_legs"] = {"headline": {"exchange": out["config"].get("grad_exchange"), "ms_per_step": out["ms_per_step"],
@@ -807,7 +814,7 @@ def worker(a):
             ab["fastest_fp32"] = {"leg": best, "ms_per_step": timed[best], "measured_on": ctx["backend_note"]}
     state["phase"] = "cpu baseline"
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline and default_headline:
+        if a.full and world == 1 and not a.no_cpu_baseline and default_headline:
             out["cpu_baseline"] = cpu_baseline(a.bl or a.bu, a.bu)
         state["done"] = True
         watchdog.cancel()

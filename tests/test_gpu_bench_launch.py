@@ -54,8 +54,8 @@ def test_four_ranks_complete_the_headline_the_tuner_and_the_exchange_legs():
     all report, and the line is complete (no watchdog truncation)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-also",
-                        "--no-roofline"], env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--repeats", "1", "--full",
+                        "--no-also", "--no-roofline"], env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
     o = json.loads(lines[0])
@@ -87,8 +87,8 @@ def test_one_forced_rank_on_rccl_prints_the_data_parallel_line():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "SR_DIST_BACKEND", "SR_GRAD_EXCHANGE",
                                                               "SRHIP_CHECK_ARGS")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dp", "--steps", "10", "--warmup", "2", "--repeats", "3", "--no-also",
-                        "--no-roofline", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dp", "--steps", "10", "--warmup", "2", "--repeats", "3", "--full",
+                        "--no-also", "--no-roofline", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
     o = json.loads(lines[0])
@@ -126,10 +126,23 @@ def test_watchdog_prints_the_headline_when_the_secondary_phases_do_not_finish():
     """After the headline is measured nothing may cost the line: with a budget the secondary legs cannot meet, every rank's watchdog ends its
     process and rank 0 prints the line with the headline fields complete (a collective that one rank never reaches does not raise)."""
     env = dict(os.environ)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "1", "--no-roofline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "1", "--full", "--no-roofline",
                         "--extra-budget", "1"], env=env,
                        capture_output=True, text=True, timeout=420, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
     o = json.loads(lines[0])
     assert "truncated" in o and o["value"] > 0 and o["n_gpus"] == 1 and o["steps"] == 3 and o["ms_per_step"] > 0
+
+
+def test_plain_run_measures_the_headline_only():
+    """Without --full the run ends at the headline: one line with the headline fields and none of what --full adds (roofline pass, secondary
+    legs, CPU baseline), and the watchdog of those phases never fires."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"], env=dict(os.environ),
+                       capture_output=True, text=True, timeout=420, cwd=ROOT)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
+    o = json.loads(lines[0])
+    assert o["n_gpus"] == 1 and o["steps"] == 3 and o["warmup"] == 1 and o["value"] > 0 and o["ms_per_step"] > 0
+    assert o["higher_is_better"] is True and o["dtype"] == "bf16" and o["unit"] == "unlabeled images/s"
+    assert not {"roofline", "also", "cpu_baseline", "grad_exchange_legs", "truncated"} & set(o), sorted(o)

@@ -1,7 +1,7 @@
 #!/bin/bash
 cd "$(dirname "$0")/.."
 O=gpurun_out
-timeout 1500 python bench.py > $O/r06_bench_full_a.json 2> $O/r06_bench_full_a.err
+timeout 1500 python bench.py --full > $O/r06_bench_full_a.json 2> $O/r06_bench_full_a.err
 python - <<'PY'
 import json
 o=json.loads([l for l in open('gpurun_out/r06_bench_full_a.json') if l.startswith('{')][-1])
