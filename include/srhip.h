@@ -560,7 +560,7 @@ int srhip_gemm_nt_dropout(int epilogue, const void* A, int lda, const void* B, i
  *   w2v_pos_stage        : group-major zero-padded bf16 copy [groups][rows_total][D/groups] of fp32 rows (frame t lands on row clip*Pp + t +
  *                          pad_left): operand of the grouped positional conv (srhip_gemm_nt_grouped_f32, lda = D/groups)
  *   w2v_weightnorm_prep  : weight_norm(dim=2) filter -> bf16 operands Wf [groups][cg][k][cg] and the tap-reversed transpose Wb; norms [k]
- *   w2v_weightnorm_bwd   : dv +=, dg += from dWf (fp32, Wf layout)
+ *   w2v_weightnorm_bwd   : dv +=, dg += from dWf (fp32, Wf layout); ws: caller-owned workspace of (D + 1) * k floats
  *   w2v_pos_finish_fwd   : x0 = dropout(LayerNorm(x + GELU(conv + bias))) fp32 + bf16 (filler rows zero); saves y, mean, rstd
  *   w2v_pos_finish_bwd   : dx0 -> dy (in place), dconv = dy * GELU'(conv + bias) fp32 [B*P, D]; dgamma +=, dbeta += */
 int srhip_w2v_conv0(int mode, const float* wave, const float* W0, const float* gamma, const float* beta, double* ws, double* ws2, void* out_bf16,
@@ -577,8 +577,8 @@ int srhip_w2v_spec_mask_fwd(float* x, const unsigned char* mask, const float* em
 int srhip_w2v_spec_mask_bwd(float* dx, const float* add, const unsigned char* mask, float* dembed, int B, int T, int P, int Padd, int D, void* stream);
 int srhip_w2v_pos_stage(const float* src, void* out, int B, int T, int P, int Pp, int D, int groups, int pad_left, long rows_total, void* stream);
 int srhip_w2v_weightnorm_prep(const float* v, const float* g, float* norms, void* Wf, void* Wb, int D, int groups, int k, void* stream);
-int srhip_w2v_weightnorm_bwd(const float* dWf, const float* v, const float* g, const float* norms, float* dv, float* dg, int D, int groups, int k,
-                             void* stream);
+int srhip_w2v_weightnorm_bwd(const float* dWf, const float* v, const float* g, const float* norms, float* dv, float* dg, float* ws, int D,
+                             int groups, int k, void* stream);
 int srhip_w2v_pos_finish_fwd(const float* x, const float* conv, const float* conv_bias, const float* gamma, const float* beta, float eps, float* x0,
                              void* x0_bf16, float* ysave, float* mean, float* rstd, int B, int T, int P, int Pp, int D, unsigned drop_key,
                              unsigned drop_thresh, float drop_scale, void* stream);

@@ -166,7 +166,7 @@ SIGNATURES = {
     "srhip_w2v_spec_mask_bwd": (I, [P, P, P, P, I, I, I, I, I, P]),
     "srhip_w2v_pos_stage": (I, [P, P, I, I, I, I, I, I, I, L, P]),
     "srhip_w2v_weightnorm_prep": (I, [P, P, P, P, P, I, I, I, P]),
-    "srhip_w2v_weightnorm_bwd": (I, [P, P, P, P, P, P, I, I, I, P]),
+    "srhip_w2v_weightnorm_bwd": (I, [P, P, P, P, P, P, P, I, I, I, P]),
     "srhip_w2v_pos_finish_fwd": (I, [P, P, P, P, P, F, P, P, P, P, P, I, I, I, I, I, U, U, F, P]),
     "srhip_w2v_pos_finish_bwd": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, U, U, F, P]),
 }

@@ -700,21 +700,21 @@ extern "C" int srhip_w2v_spec_mask_fwd(float* x, const unsigned char* mask, cons
 }
 extern "C" int srhip_w2v_spec_mask_bwd(float* dx, const float* add, const unsigned char* mask, float* dembed, int B, int T, int P, int Padd, int D,
                                        void* stream) {
-  if (!dx || B <= 0 || D % 64 || (mask && !dembed)) return SR_EINVAL;
+  if (!dx || B <= 0 || D <= 0 || D % 64 || (mask && !dembed)) return SR_EINVAL;
   SR_LAUNCH(spec_mask_bwd_kernel, dim3(D / 64, B), dim3(256), 0, (hipStream_t)stream, dx, add, mask, dembed, T, P, Padd, D);
   SR_CHECK_LAUNCH();
   return SR_OK;
 }
 extern "C" int srhip_w2v_pos_stage(const float* src, void* out, int B, int T, int P, int Pp, int D, int groups, int pad_left, long rows_total,
                                    void* stream) {
-  if (!src || !out || B <= 0 || D % groups || ((D / groups) & 7) || rows_total < (long)B * Pp || (((uintptr_t)src | (uintptr_t)out) & 15)) return SR_EINVAL;
+  if (!src || !out || B <= 0 || D <= 0 || groups <= 0 || D % groups || ((D / groups) & 7) || rows_total < (long)B * Pp || (((uintptr_t)src | (uintptr_t)out) & 15)) return SR_EINVAL;
   const long n = rows_total * (D / 8);
   W2V_LAUNCH1D(pos_stage_kernel, n, src, (bf16_t*)out, B, T, P, Pp, D, D / groups, pad_left, rows_total, n);
   SR_CHECK_LAUNCH();
   return SR_OK;
 }
 extern "C" int srhip_w2v_weightnorm_prep(const float* v, const float* g, float* norms, void* Wf, void* Wb, int D, int groups, int k, void* stream) {
-  if (!v || !g || !norms || !Wf || !Wb || D % groups) return SR_EINVAL;
+  if (!v || !g || !norms || !Wf || !Wb || D <= 0 || groups <= 0 || k <= 0 || D % groups) return SR_EINVAL;
   const int cg = D / groups;
   SR_LAUNCH(wn_norm_kernel, dim3(k), dim3(256), 0, (hipStream_t)stream, v, norms, D * cg, k);
   SR_CHECK_LAUNCH();
@@ -722,23 +722,15 @@ extern "C" int srhip_w2v_weightnorm_prep(const float* v, const float* g, float* 
   SR_CHECK_LAUNCH();
   return SR_OK;
 }
-extern "C" int srhip_w2v_weightnorm_bwd(const float* dWf, const float* v, const float* g, const float* norms, float* dv, float* dg, int D, int groups,
-                                        int k, void* stream) {
-  if (!dWf || !v || !g || !norms || !dv || !dg || D % groups) return SR_EINVAL;
+extern "C" int srhip_w2v_weightnorm_bwd(const float* dWf, const float* v, const float* g, const float* norms, float* dv, float* dg, float* ws, int D,
+                                        int groups, int k, void* stream) {
+  if (!dWf || !v || !g || !norms || !dv || !dg || !ws || D <= 0 || groups <= 0 || k <= 0 || D % groups) return SR_EINVAL;
   const int cg = D / groups;
   const size_t lds = ((size_t)k * (cg + 1) + 256) * sizeof(float);
-  if (k > 0 && 256 % k == 0 && lds <= 64 * 1024) {
-    // library-owned scratch for the per-channel partial sums and the per-tap dots ((D + 1) * k floats; one backward at a time per process)
-    static float* scratch = nullptr;
-    static size_t scratch_n = 0;
-    const size_t need = ((size_t)D + 1) * k;
-    if (need > scratch_n) {
-      if (scratch) (void)hipFree(scratch);
-      if (hipMalloc(&scratch, need * sizeof(float)) != hipSuccess) { scratch = nullptr; scratch_n = 0; return SR_ELAUNCH; }
-      scratch_n = need;
-    }
-    float* partial = scratch;
-    float* dot = scratch + (size_t)D * k;
+  if (256 % k == 0 && lds <= 64 * 1024) {
+    // caller-owned workspace ((D + 1) * k floats): the per-channel partial sums, then the per-tap dots
+    float* partial = ws;
+    float* dot = ws + (size_t)D * k;
     hipStream_t st = (hipStream_t)stream;
     if (lds > 48 * 1024) {
       (void)hipFuncSetAttribute((const void*)wn_bwd_dot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

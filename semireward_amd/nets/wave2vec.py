@@ -115,6 +115,33 @@ def spec_augment_mask(rng, B, T, mask_prob, mask_length, min_masks):
     return m
 
 
+def conv_dw_chunks(C, conv_kernel, B, P):
+    """Frame chunks of the grouped weight-gradient launch of the conv layers 1.. (host logic, no launch): the reduction over the B * P[l] frame
+    rows of layer l is split into chunks of CH rows, each a C x k*C partial product (a 512 x 1536 product is 48 tiles; at 100 000 frames it
+    would run on 48 CUs for a millisecond).  C a multiple of 256: the launch goes to the 256 x 256 persistent kernel
+    (srhip_gemm_tn_grouped_pp_f32), whose walk is static -- workgroup w takes tiles w, w + 256, ...: the chunk is the shortest (>= 1024 frames,
+    a multiple of 64) that gives at most ``rounds`` x 256 tiles, so that every workgroup multiplies about the same number of K-tiles (8 clips:
+    5120 frames per chunk, 256 tiles, one round; the 128 x 128 kernel took 785 us for this launch with chunks of 12800: 1168 tiles = 1.5 rounds
+    of its 768 slots at 0.9 us per k-step).  ``rounds`` is at least the rounds that one chunk per layer needs, so the search ends (once CH
+    covers the longest layer at the latest).  Otherwise the 128 x 128 kernel with chunks of 12800 rows.
+    Returns SimpleNamespace(pp, CH, rounds, tiles_l [tiles of one chunk of layer l], chunks [per layer: [(first row, rows)]]; layer 0 empty)."""
+    nl = len(conv_kernel)
+    R = [B * P[l] for l in range(nl)]
+    pp = C % 256 == 0
+    if pp:
+        tiles_l = [0] + [(C // 256) * (-(-(conv_kernel[l] * C) // 256)) for l in range(1, nl)]
+        total = sum(tiles_l[l] * R[l] for l in range(1, nl))                               # tile-frames
+        rounds = max(1, -(-total // (256 * 8192)), -(-sum(tiles_l) // 256))               # at most ~8192 frames per tile and round
+        CH = 1024
+        while sum(tiles_l[l] * -(-R[l] // CH) for l in range(1, nl)) > 256 * rounds:
+            CH += 64
+    else:
+        tiles_l = [0] + [(C // 128) * (-(-(conv_kernel[l] * C) // 128)) for l in range(1, nl)]
+        rounds, CH = 0, 12800
+    chunks = [[]] + [[(r0, min(CH, R[l] - r0)) for r0 in range(0, R[l], CH)] for l in range(1, nl)]
+    return types.SimpleNamespace(pp=pp, CH=CH, rounds=rounds, tiles_l=tiles_l, chunks=chunks)
+
+
 class ClassificationWave2Vec(PostLNEncoderMixin):
     def __init__(self, cfg=None, device="cuda", **kw):
         self.cfg = cfg if cfg is not None else W2vConfig(**kw)
@@ -368,33 +395,21 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
         t.dpre = [None] + [torch.zeros(B * P[l] + 16, C, dtype=bf16, device=dev) for l in range(1, nl)]
         t.dY0 = torch.zeros(B * P[0] + 16, C, dtype=bf16, device=dev)
         t.dcol = [None] + [torch.empty(B * P[l], cfg.conv_kernel[l] * C, dtype=bf16, device=dev) for l in range(1, nl)]
-        # weight gradients of the conv layers 1..: ONE grouped launch, the reduction over the frames split into chunks of CH rows (a
-        # 512 x 1536 product is 48 tiles; at 100 000 frames it would run on 48 CUs for a millisecond) -> partial products, summed by wgrad_add
-        # C a multiple of 256: the launch goes to the 256 x 256 persistent kernel (srhip_gemm_tn_grouped_pp_f32), whose walk is static -- workgroup w
-        # takes tiles w, w + 256, ...: the chunk is the shortest (>= 1024 frames, a multiple of 64) that gives at most `rounds` x 256 tiles, so
-        # that every workgroup multiplies about the same number of K-tiles (8 clips: 5120 frames per chunk, 256 tiles, one round; the 128 x 128
-        # kernel took 785 us for this launch with chunks of 12800: 1168 tiles = 1.5 rounds of its 768 slots at 0.9 us per k-step)
-        t.conv_dw_pp = C % 256 == 0
-        if t.conv_dw_pp:
-            tiles_l = [0] + [(C // 256) * (-(-(cfg.conv_kernel[l] * C) // 256)) for l in range(1, nl)]
-            total = sum(tiles_l[l] * (B * P[l]) for l in range(1, nl))                      # tile-frames
-            rounds = max(1, -(-total // (256 * 8192)))                                     # at most ~8192 frames per tile and round
-            CH = 1024
-            while sum(tiles_l[l] * -(-(B * P[l]) // CH) for l in range(1, nl)) > 256 * rounds:
-                CH += 64
-        else:
-            CH = 12800
-        t.dW_parts = [0] + [-(-(B * P[l]) // CH) for l in range(1, nl)]
+        # weight gradients of the conv layers 1..: ONE grouped launch, the reduction over the frames split into chunks (conv_dw_chunks) ->
+        # partial products, summed by wgrad_add
+        plan = conv_dw_chunks(C, cfg.conv_kernel, B, P)
+        t.conv_dw_pp = plan.pp
+        t.dW_parts = [0] + [len(plan.chunks[l]) for l in range(1, nl)]
         t.dWr = [None] + [torch.empty(t.dW_parts[l], C, cfg.conv_kernel[l] * C, dtype=f32, device=dev) for l in range(1, nl)]
         probs = []
         for l in range(1, nl):
-            kk, ss, R = cfg.conv_kernel[l], cfg.conv_stride[l], B * P[l]
-            for c_ in range(t.dW_parts[l]):
-                r0 = c_ * CH
+            kk, ss = cfg.conv_kernel[l], cfg.conv_stride[l]
+            for c_, (r0, n) in enumerate(plan.chunks[l]):
                 probs.append((ops._pa(t.dpre[l], r0 * C), C, ops._pa(f.act[l - 1], r0 * ss * C), ss * C, ops._pa(t.dWr[l], c_ * C * kk * C), kk * C, 0,
-                              C, kk * C, min(CH, R - r0)))
+                              C, kk * C, n))
         t.conv_dw = ops.make_group_tn_desc_ld(probs, dev, tile=256 if t.conv_dw_pp else 128)
         t.ws2 = torch.zeros(B, C, 2, dtype=torch.float64, device=dev)
+        t.wn_ws = torch.empty(ops.w2v_weightnorm_ws_floats(D, k), dtype=f32, device=dev)
         self._buf_cache[key] = t
         return t
 
@@ -419,7 +434,8 @@ class ClassificationWave2Vec(PostLNEncoderMixin):
         desc, npb, ntiles, flops, nbytes = t.pos_dw
         ops.gemm_tn_grouped_f32(desc, npb, ntiles, alpha=1.0, beta=0.0, flops=flops, nbytes=nbytes)
         ops.w2v_weightnorm_bwd(t.dWf, Pm(PC + "parametrizations.weight.original1"), Pm(PC + "parametrizations.weight.original0"), self.pos_norms,
-                               G(PC + "parametrizations.weight.original1"), G(PC + "parametrizations.weight.original0"), D, cfg.pos_groups, cfg.pos_k)
+                               G(PC + "parametrizations.weight.original1"), G(PC + "parametrizations.weight.original0"), t.wn_ws, D, cfg.pos_groups,
+                               cfg.pos_k)
         desc, npb, ntiles, flops, nbytes = t.pos_dx
         ops.gemm_nt_grouped_f32(desc, npb, ntiles, alpha=1.0, beta=0.0, flops=flops, nbytes=nbytes, n64=D // cfg.pos_groups <= 64)
         # ---- SpecAugment, projection (dropout' folded into the bf16 cast of the branch gradient)

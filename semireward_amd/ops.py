@@ -1248,8 +1248,14 @@ def w2v_weightnorm_prep(v, g, norms, Wf, Wb, D, groups, k):
     _call("srhip_w2v_weightnorm_prep", _p(v), _p(g), _p(norms), _p(Wf), _p(Wb), D, groups, k, _s())
 
 
-def w2v_weightnorm_bwd(dWf, v, g, norms, dv, dg, D, groups, k):
-    _call("srhip_w2v_weightnorm_bwd", _p(dWf), _p(v), _p(g), _p(norms), _p(dv), _p(dg), D, groups, k, _s())
+def w2v_weightnorm_bwd(dWf, v, g, norms, dv, dg, ws, D, groups, k):
+    """dv +=, dg += ; ws: fp32 workspace of at least (D + 1) * k elements (w2v_weightnorm_ws_floats)."""
+    assert ws.numel() >= w2v_weightnorm_ws_floats(D, k)
+    _call("srhip_w2v_weightnorm_bwd", _p(dWf), _p(v), _p(g), _p(norms), _p(dv), _p(dg), _p(ws), D, groups, k, _s())
+
+
+def w2v_weightnorm_ws_floats(D, k):
+    return (D + 1) * k
 
 
 def w2v_pos_finish_fwd(x, conv, cbias, gamma, beta, eps, x0, x0b, ysave, mean, rstd, B, T, P, Pp, D, drop=None):
@@ -1264,8 +1270,10 @@ def w2v_pos_finish_bwd(dx0, ysave, conv, cbias, mean, rstd, gamma, dconv, dgamma
 
 def make_group_desc_ld(problems, device, bn=128):
     """srhip_group_desc table with explicit leading dimensions / raw pointers: problems = list of (A_ptr, lda, B_ptr, ldb, C_ptr, ldc, M, N, K).
-    bn = 64: the table of srhip_gemm_nt_grouped_n64_f32 (128 x 64 tiles; gemm_nt_grouped_f32(..., n64=True))."""
+    bn = 64: the table of srhip_gemm_nt_grouped_n64_f32 (128 x 64 tiles; gemm_nt_grouped_f32(..., n64=True)).
+    The kernels walk K in steps of 32 and read no partial step (srhip.h: K % 32 == 0): a table that breaks that is refused here, on the host."""
     import numpy as np
+    assert all(pr[8] > 0 and pr[8] % 32 == 0 for pr in problems), "grouped products need K % 32 == 0 (srhip.h)"
     arr = np.zeros(len(problems), dtype=GROUP_DESC_DTYPE)
     t = 0
     for i, (A, lda, B, ldb, C, ldc, M, N, K) in enumerate(problems):

@@ -3,6 +3,7 @@ without a GPU), host-side logic (chunk table, layer-decay table, scheduler, pass
 import ctypes
 import os
 import re
+import types
 
 import numpy as np
 import pytest
@@ -43,6 +44,28 @@ def test_invalid_arguments_return_error_codes_without_gpu():
     assert lib.srhip_attn_fwd(None, None, None, 1, 1000, 6, 0.125, None) == -1
     assert lib.srhip_layernorm_fwd(None, None, None, 1e-6, None, None, None, 4, 100, None) == -1
     assert lib.srhip_rewarder_fwd(None, None, None, None, None, None, 2, 8, 384, 100, 1, None) == -1     # save needs G == 1
+    # audio front end (w2v_ops.hip): the guards reject before any launch.  The pointers are 16-byte aligned host addresses that are never
+    # dereferenced; a misaligned one is rejected by the col2im guard itself.
+    a = 0x10000
+    E = -1                                                                                                # SR_EINVAL
+    assert lib.srhip_w2v_col2im_dgelu(a, None, a, 2, 8, 16, 132, 3, 2, None) == E                         # C % 8 != 0
+    assert lib.srhip_w2v_col2im_dgelu(a + 2, None, a, 2, 8, 16, 128, 3, 2, None) == E                     # dcol misaligned
+    assert lib.srhip_w2v_col2im_dgelu(a, a + 8, a, 2, 8, 16, 128, 3, 2, None) == E                        # pre_prev misaligned
+    assert lib.srhip_w2v_col2im_dgelu(a, None, a + 4, 2, 8, 16, 128, 3, 2, None) == E                     # out misaligned
+    assert lib.srhip_w2v_pos_stage(a, a, 2, 10, 16, 32, 96, 16, 8, 80, None) == E                         # D / groups = 6: % 8 != 0
+    assert lib.srhip_w2v_pos_stage(a, a, 2, 10, 16, 32, 128, 0, 8, 80, None) == E                         # no groups
+    assert lib.srhip_w2v_weightnorm_prep(a, a, a, a, a, 100, 16, 128, None) == E                          # D % groups != 0
+    assert lib.srhip_w2v_weightnorm_bwd(a, a, a, a, a, a, a, 100, 16, 128, None) == E                     # D % groups != 0
+    assert lib.srhip_w2v_weightnorm_bwd(a, a, a, a, a, a, None, 768, 16, 128, None) == E                  # no workspace
+    assert lib.srhip_w2v_weightnorm_bwd(a, a, a, a, a, a, a, 768, 0, 128, None) == E                      # no groups
+    for C in (64, 192, 640, 1024):                                                                        # featln: 128 / 256 / 512 / 768
+        assert lib.srhip_w2v_featln_fwd(a, a, a, 1e-5, a, a, a, 2, 10, 16, C, None) == E
+        assert lib.srhip_w2v_featln_bwd(a, a, a, a, a, a, a, a, a, 2, 10, 16, C, None) == E
+    for D in (256, 512, 1024):                                                                            # pos_finish: 128 / 384 / 768
+        assert lib.srhip_w2v_pos_finish_fwd(a, a, a, a, a, 1e-5, a, a, a, a, a, 2, 10, 16, 16, D, 0, 0, 1.0, None) == E
+        assert lib.srhip_w2v_pos_finish_bwd(a, a, a, a, a, a, a, a, a, a, 2, 10, 16, 16, D, 0, 0, 1.0, None) == E
+    assert lib.srhip_w2v_spec_mask_bwd(a, None, None, None, 2, 10, 16, 16, 96, None) == E                 # D % 64 != 0
+    assert lib.srhip_w2v_spec_mask_bwd(a, None, a, None, 2, 10, 16, 16, 128, None) == E                   # mask without dembed
     with pytest.raises(RuntimeError):
         _lib.check(-1, "x")
 
@@ -442,3 +465,38 @@ def test_weight_gradient_table_of_the_persistent_kernel_is_balanced_on_the_host(
     vit = [(0, 0, 0, 0, 384, 1536, 4112), (0, 0, 0, 0, 1536, 384, 4112), (0, 0, 0, 0, 384, 384, 4112), (0, 0, 0, 0, 1152, 384, 4112)]
     assert 0.70 < ops.tn_pp_efficiency(vit) < 0.72
 
+
+
+@pytest.mark.parametrize("samples", [64000, 16001])
+def test_conv_weight_gradient_chunks_cover_every_frame_once(samples):
+    """wave2vec.conv_dw_chunks (host logic of the conv layers' weight-gradient table, no launch): the search returns for every width -- at
+    C = 1280 one chunk per layer is already more than one round of the persistent kernel (400 tiles), which made the old search spin forever --
+    every frame row of every layer lies in exactly one chunk, and on the persistent (256 x 256) path the table has at most 256 x rounds tiles."""
+    from semireward_amd.nets import wave2vec
+    cfg = wave2vec.W2vConfig()
+    geo = wave2vec.ClassificationWave2Vec.geometry(types.SimpleNamespace(cfg=cfg), samples)
+    T, P = geo[0], geo[1]
+    nl = len(cfg.conv_kernel)
+    for C in (128, 256, 512, 768, 1024, 1280):
+        for B in (1, 2, 8):
+            plan = wave2vec.conv_dw_chunks(C, cfg.conv_kernel, B, P)
+            assert plan.pp == (C % 256 == 0) and plan.chunks[0] == []
+            tiles = 0
+            for l in range(1, nl):
+                seen = np.zeros(B * P[l], dtype=np.int32)
+                for r0, n in plan.chunks[l]:
+                    assert n > 0 and r0 >= 0 and r0 + n <= B * P[l]
+                    seen[r0:r0 + n] += 1
+                assert (seen == 1).all(), (C, B, l)
+                side = 256 if plan.pp else 128
+                tiles += len(plan.chunks[l]) * (C // side) * -(-(cfg.conv_kernel[l] * C) // side)
+            if plan.pp:
+                assert plan.CH >= 1024 and plan.CH % 64 == 0
+                assert tiles <= 256 * plan.rounds, (C, B, tiles, plan.rounds)
+                # rounds is not inflated: it is what the frames ask for, or what one chunk per layer needs
+                need = max(1, -(-sum(plan.tiles_l[l] * B * P[l] for l in range(1, nl)) // (256 * 8192)), -(-sum(plan.tiles_l) // 256))
+                assert plan.rounds == need
+    # the flagship shape keeps its plan: 8 clips of 64000 samples, C = 512 -> chunks of 5120 frames, one round of 256 tiles
+    if samples == 64000:
+        plan = wave2vec.conv_dw_chunks(512, cfg.conv_kernel, 8, P)
+        assert (plan.CH, plan.rounds) == (5120, 1) and [len(c) for c in plan.chunks[1:]] == [10, 5, 3, 2, 1, 1]
