@@ -225,7 +225,8 @@ int srhip_patch_embed_fwd(const float* img, const int* img_index, const float* W
 int srhip_patch_embed_bwd(const float* dx, const float* img, const int* img_index, float* dWp, float* dbp, float* dcls,
                           float* dpos, int B, int C, int HW, int ps, int D, void* stream);
 /* The same without atomics on the filter: per-(token chunk, image) partial sums in ws (srhip_patch_embed_bwd_ws_floats(...) floats), folded
- * by a second launch in a fixed order (deterministic; the one-launch form ends every workgroup in D * (K + 1) same-address atomics). */
+ * by a second launch in a fixed order (deterministic; the one-launch form ends every workgroup in D * (K + 1) same-address atomics).
+ * srhip_patch_embed_bwd_ws_floats returns -1 for a shape the launches refuse (K > 64, ps <= 0, D % 64 != 0, D > 1024, ...). */
 long srhip_patch_embed_bwd_ws_floats(int B, int C, int HW, int ps, int D);
 int srhip_patch_embed_bwd_ws(const float* dx, const float* img, const int* img_index, float* dWp, float* dbp, float* dcls,
                              float* dpos, float* ws, int B, int C, int HW, int ps, int D, void* stream);
@@ -355,7 +356,7 @@ int srhip_droppath_fill_cols(float* out, const float* probs, const long long* co
  *                     launch already wrote.  In place: sources and destinations are disjoint.
  *   srhip_vit_fanout: after the head, column g (g < n_cols) of the step's tables takes its node's outputs:
  *                     logits_all[col_rows[g], :C] = node_logits[col_node[g], :], feat_all[col_rows[g], :D] = node_feat[col_node[g], :]
- *                     (node tables [n_nodes, .], step tables [rows_all, .]).
+ *                     (node tables [n_nodes, .], step tables [rows_all, .]: rows_all bounds both, so pass the shorter table's rows).
  * Index entries out of range copy nothing.  Pure copies (16-byte accesses where slabs and bases allow): results are the unshared launch's. */
 int srhip_vit_fork(float* x, void* ln, const int* parent, int n_new, int dst0, int rows_per_node, int D, void* stream);
 int srhip_vit_fanout(const float* node_logits, const float* node_feat, int n_nodes, const int* col_node, const long long* col_rows,

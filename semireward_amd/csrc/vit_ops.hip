@@ -686,9 +686,15 @@ extern "C" int srhip_ln_grad_reduce(const srhip_ln_reduce_desc* desc_dev, float*
   return SR_OK;
 }
 
+// The small-patch embedding kernels: one thread per feature (D % 64 == 0, D <= 1024), the patch (K = C * ps * ps <= 64 taps) in registers.
+// ps is tested before HW % ps: a zero patch size must be refused, not divided by.
+static bool pe_shape_ok(int B, int C, int HW, int ps, int D) {
+  return B > 0 && C > 0 && ps > 0 && HW > 0 && HW % ps == 0 && D > 0 && D % 64 == 0 && D <= 1024 && C * ps * ps <= 64;
+}
+
 extern "C" int srhip_patch_embed_fwd(const float* img, const int* img_index, const float* Wp, const float* bp, const float* cls,
                                      const float* pos, float* x, int B, int C, int HW, int ps, int D, void* stream) {
-  if (B <= 0 || HW % ps || D % 64 || D > 1024 || C * ps * ps > 64) return SR_EINVAL;
+  if (!pe_shape_ok(B, C, HW, ps, D)) return SR_EINVAL;
   const int gw = HW / ps, N = gw * gw + 1, K = C * ps * ps;
   SR_LAUNCH(patch_embed_fwd_kernel, dim3(cdiv(N, PE_TOK), B), dim3(D), PE_TOK * K * sizeof(float), (hipStream_t)stream,
                      img, img_index, Wp, bp, cls, pos, x, C, HW, ps, D);
@@ -698,7 +704,7 @@ extern "C" int srhip_patch_embed_fwd(const float* img, const int* img_index, con
 
 extern "C" int srhip_patch_embed_bwd(const float* dx, const float* img, const int* img_index, float* dWp, float* dbp,
                                      float* dcls, float* dpos, int B, int C, int HW, int ps, int D, void* stream) {
-  if (B <= 0 || HW % ps || D % 64 || D > 1024 || C * ps * ps > 64) return SR_EINVAL;
+  if (!pe_shape_ok(B, C, HW, ps, D)) return SR_EINVAL;
   const int gw = HW / ps, N = gw * gw + 1, K = C * ps * ps;
   hipStream_t s = (hipStream_t)stream;
   SR_LAUNCH(patch_embed_bwd_pos_kernel, dim3(N), dim3(D), 0, s, dx, dpos, dcls, B, N, D);
@@ -710,13 +716,13 @@ extern "C" int srhip_patch_embed_bwd(const float* dx, const float* img, const in
 }
 
 extern "C" long srhip_patch_embed_bwd_ws_floats(int B, int C, int HW, int ps, int D) {
-  if (B <= 0 || ps <= 0 || HW % ps) return -1;
+  if (!pe_shape_ok(B, C, HW, ps, D)) return -1;              // the shapes srhip_patch_embed_bwd_ws refuses have no workspace size
   const int gw = HW / ps, K = C * ps * ps;
   return (long)cdiv(gw * gw, PE_TOK) * B * (K + 1) * D;
 }
 extern "C" int srhip_patch_embed_bwd_ws(const float* dx, const float* img, const int* img_index, float* dWp, float* dbp, float* dcls,
                                         float* dpos, float* ws, int B, int C, int HW, int ps, int D, void* stream) {
-  if (B <= 0 || HW % ps || D % 64 || D > 1024 || C * ps * ps > 64 || !ws) return SR_EINVAL;
+  if (!pe_shape_ok(B, C, HW, ps, D) || !ws) return SR_EINVAL;
   const int gw = HW / ps, N = gw * gw + 1, K = C * ps * ps, nch = cdiv(N - 1, PE_TOK);
   hipStream_t s = (hipStream_t)stream;
   SR_LAUNCH(patch_embed_bwd_pos_kernel, dim3(N), dim3(D), 0, s, dx, dpos, dcls, B, N, D);
@@ -748,7 +754,9 @@ extern "C" int srhip_cls_head_fwd_scatter(const float* x, const float* gamma, co
 extern "C" int srhip_cls_head_bwd(const float* dlogits, const float* Wh, const float* gamma, const float* feat,
                                   const float* xhat, const float* rstd, float* dx, float* dWh, float* dbh, float* dgamma,
                                   float* dbeta, int B, int N, int D, int C, void* stream) {
-  if (B <= 0 || D > 1024 || C <= 0 || (!dx && !dWh)) return SR_EINVAL;
+  if (B <= 0 || D > 1024 || C <= 0 || (!dx && !dWh) || !dlogits) return SR_EINVAL;
+  if (dx && (!Wh || !gamma || !xhat || !rstd || !dgamma || !dbeta)) return SR_EINVAL;     // each half needs all of its operands
+  if (dWh && (!dbh || !feat)) return SR_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (dx) {               // per-image half: dx of the cls rows, final-norm affine gradients (atomic adds)
     SR_LAUNCH(cls_head_bwd_x_kernel, dim3(B), dim3(256), (C + 4) * sizeof(float), s, dlogits, Wh, gamma, xhat, rstd, dx,

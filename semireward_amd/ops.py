@@ -566,7 +566,10 @@ def patch_embed_bwd(dx, img, img_index, dWp, dbp, dcls, dpos, B, C, HW, ps, D):
 
 
 def patch_embed_bwd_ws_floats(B, C, HW, ps, D):
-    return int(_lib.lib().srhip_patch_embed_bwd_ws_floats(B, C, HW, ps, D))
+    n = int(_lib.lib().srhip_patch_embed_bwd_ws_floats(B, C, HW, ps, D))
+    if n < 0:
+        raise ValueError("srhip_patch_embed_bwd_ws refuses B=%d C=%d HW=%d ps=%d D=%d" % (B, C, HW, ps, D))
+    return n
 
 
 def patch_embed_bwd_ws(dx, img, img_index, dWp, dbp, dcls, dpos, ws, B, C, HW, ps, D):
@@ -744,9 +747,10 @@ def vit_fork(x, ln, parent, n_new, dst0, rows_per_node, D):
 
 
 def vit_fanout(node_logits, node_feat, n_nodes, col_node, col_rows, n_cols, logits_all, feat_all, C, D):
-    """logits_all[col_rows[g]] = node_logits[col_node[g]], feat_all[col_rows[g]] = node_feat[col_node[g]] for g < n_cols (srhip_vit_fanout)."""
+    """logits_all[col_rows[g]] = node_logits[col_node[g]], feat_all[col_rows[g]] = node_feat[col_node[g]] for g < n_cols (srhip_vit_fanout).
+    A row is written in both tables, so it is bounded by the shorter of the two."""
     _call("srhip_vit_fanout", _p(node_logits), _p(node_feat), n_nodes, _p(col_node), _p(col_rows), n_cols, _p(logits_all), _p(feat_all),
-          logits_all.shape[0], C, D, _s())
+          min(logits_all.shape[0], feat_all.shape[0]), C, D, _s())
 
 
 # ---- score filter -----------------------------------------------------------------------------

@@ -66,6 +66,39 @@ def test_invalid_arguments_return_error_codes_without_gpu():
         assert lib.srhip_w2v_pos_finish_bwd(a, a, a, a, a, a, a, a, a, a, 2, 10, 16, 16, D, 0, 0, 1.0, None) == E
     assert lib.srhip_w2v_spec_mask_bwd(a, None, None, None, 2, 10, 16, 16, 96, None) == E                 # D % 64 != 0
     assert lib.srhip_w2v_spec_mask_bwd(a, None, a, None, 2, 10, 16, 16, 128, None) == E                   # mask without dembed
+    # ViT glue and backward (vit_ops.hip, precise_bwd.hip, pass_tree.hip), same pattern
+    for fn in (lib.srhip_layernorm_bwd_part, lib.srhip_layernorm_bwd_part_f32):
+        assert fn(a, a, a, a, a, a, a, 0, a, None, 0, 4112, 384, None) == E                               # n_rep = 0
+        assert fn(a, a, a, a, a, a, None, 16, a, None, 0, 4112, 384, None) == E                           # no partial copies
+        assert fn(a, a, a, a, a, a, a, 16, a, None, 0, 4112, 256, None) == E                              # D = 256 has no instantiation
+        assert fn(a, a, a, a, a, a, a, 16, a, a, 0, 4112, 384, None) == E                                 # row_scale with rps = 0
+    assert lib.srhip_ln_grad_reduce(a, a, 0, 16, 384, None) == E                                          # n_ln = 0
+    assert lib.srhip_ln_grad_reduce(a, a, 24, 0, 384, None) == E                                          # n_rep = 0
+    assert lib.srhip_patch_embed_bwd_ws(a, a, None, a, a, a, a, None, 16, 3, 32, 2, 384, None) == E       # no workspace
+    assert lib.srhip_patch_embed_bwd_ws(a, a, None, a, a, a, a, a, 16, 3, 32, 6, 384, None) == E          # K = 108 > 64
+    for shape in [(16, 3, 32, 6, 384), (16, 3, 32, 0, 384), (16, 0, 32, 2, 384), (16, 3, 32, 2, 352), (16, 3, 32, 2, 2048),
+                  (16, 3, 30, 4, 384), (0, 3, 32, 2, 384)]:
+        # K > 64, ps = 0 (was a host division by zero), C = 0, D % 64, D > 1024, HW % ps, B = 0: refused by every small-patch entry point,
+        # and the workspace size of a refused shape is -1
+        assert lib.srhip_patch_embed_bwd_ws_floats(*shape) == -1, shape
+        assert lib.srhip_patch_embed_bwd_ws(a, a, None, a, a, a, a, a, *shape, None) == E, shape
+        assert lib.srhip_patch_embed_bwd(a, a, None, a, a, a, a, *shape, None) == E, shape
+        assert lib.srhip_patch_embed_fwd(a, None, a, a, a, a, a, *shape, None) == E, shape
+    assert lib.srhip_patch_embed_bwd_ws_floats(16, 3, 32, 2, 384) == 8 * 16 * 13 * 384                    # 8 chunks x 16 images x (K + 1) x D
+    for fn in (lib.srhip_patch_im2col, lib.srhip_patch_im2col_f32):
+        assert fn(a, None, a, 2, 3, 225, 15, None) == E                                                   # odd ps
+    assert lib.srhip_patch_grad_operands(a, a, a, a, 2, 196, 383, None) == E                              # odd D
+    assert lib.srhip_patch_grad_operands_f32(a, a, a, a, 2, 196, 383, None) == E
+    assert lib.srhip_scale_rows_f32(a + 4, None, 0, a, 4112, 384, None) == E                              # x misaligned
+    assert lib.srhip_scale_rows_f32(a, None, 0, a, 4112, 382, None) == E                                  # D % 4 != 0
+    assert lib.srhip_scale_rows_f32(a, a, 0, a, 4112, 384, None) == E                                     # scale with rps = 0
+    assert lib.srhip_vit_fork(a, a, a, 4, 0, 257, 384, None) == E                                         # dst0 = 0
+    assert lib.srhip_vit_fanout(a, a, 0, a, a, 4, a, a, 32, 10, 384, None) == E                           # n_nodes = 0
+    # cls head backward: each half needs all of its operands
+    assert lib.srhip_cls_head_bwd(a, a, a, None, a, a, a, None, None, None, a, 16, 257, 384, 100, None) == E   # dx without dgamma
+    assert lib.srhip_cls_head_bwd(a, None, a, None, a, a, a, None, None, a, a, 16, 257, 384, 100, None) == E   # dx without Wh
+    assert lib.srhip_cls_head_bwd(a, None, None, None, None, None, None, a, None, None, None, 16, 257, 384, 100, None) == E  # dWh, no dbh
+    assert lib.srhip_cls_head_bwd(a, None, None, None, None, None, None, a, a, None, None, 16, 257, 384, 100, None) == E     # no feat
     with pytest.raises(RuntimeError):
         _lib.check(-1, "x")
 
