@@ -424,6 +424,30 @@ int srhip_reward_mask2(const float* reward, float* mask2, float* mean_out, const
  * consistency.py:38-45): loss = mean_B(nll*mask*mask2); dlogits = grad_scale*(softmax-onehot)*mask*mask2/B. */
 int srhip_masked_ce(const float* logits, const long long* targets, const float* mask, const float* mask2, float grad_scale,
                     float* loss_out, float* dlogits, int B, int C, void* stream);
+/* The rest of the criterion surface (criterions.hip), forward + analytic backward, one wave per row, fp32, fixed-order batch reduction
+ * (run-to-run bit-identical).  Per row b, with w_b = mask[b] * mask2[b] (each optional):
+ *   ce_hard:          l_b = -log_softmax(z_b)[y_b]                       d l_b / d z = softmax(z_b) - onehot(y_b)
+ *   ce_soft:          l_b = sum_c -t_bc log_softmax(z_b)_c               d l_b / d z = softmax(z_b) * sum_c t_bc - t_b   (t not normalised)
+ *   consistency_mse:  p = softmax(z_b), l_b = mean_c (p_c - t_bc)^2      d l_b / d z = (2 / C) p * ((p - t_b) - sum_c p_c (p_c - t_bc))
+ *   consistency_l1:   l_b = mean_c |z_bc - t_bc|                         d l_b / d z = sign(z_b - t_b) / C, sign(0) = 0
+ * logits fp32 [B, C] with row stride ld (elements, >= C); soft targets fp32 [B, C] with row stride ldt; hard targets int64 [B].
+ * loss_rows (optional, [B]) = l_b * w_b.  loss (optional, [1]) = sum_b l_b w_b, divided by B for SRHIP_REDUCE_MEAN (over ALL rows, as
+ * consistency.py:45).  dlogits (optional, row stride ldd; NULL = no gradient) = grad_scale * w_b * r * d l_b / d z with r = 1 / B for
+ * MEAN and 1 for SUM and NONE (for NONE the caller's per-row upstream weights go in through mask).  B <= 64 rows, or loss without
+ * loss_rows, run as ONE workgroup and one launch; otherwise one row per wave across the device plus a one-workgroup reduction of loss_rows. */
+#define SRHIP_REDUCE_NONE 0
+#define SRHIP_REDUCE_MEAN 1
+#define SRHIP_REDUCE_SUM 2
+int srhip_ce_hard(const float* logits, long long ld, const long long* targets, const float* mask, const float* mask2, float grad_scale,
+                  int reduction, float* loss_rows, float* loss, float* dlogits, long long ldd, int B, int C, void* stream);
+int srhip_ce_soft(const float* logits, long long ld, const float* targets, long long ldt, const float* mask, const float* mask2,
+                  float grad_scale, int reduction, float* loss_rows, float* loss, float* dlogits, long long ldd, int B, int C, void* stream);
+int srhip_consistency_mse(const float* logits, long long ld, const float* targets, long long ldt, const float* mask, const float* mask2,
+                          float grad_scale, int reduction, float* loss_rows, float* loss, float* dlogits, long long ldd, int B, int C,
+                          void* stream);
+int srhip_consistency_l1(const float* logits, long long ld, const float* targets, long long ldt, const float* mask, const float* mask2,
+                         float grad_scale, int reduction, float* loss_rows, float* loss, float* dlogits, long long ldd, int B, int C,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Rewarder / Generator (K10, K14, K15).  params: flat fp32 block in named_parameters() order.

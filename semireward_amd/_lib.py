@@ -18,6 +18,7 @@ EPI_BF16, EPI_GELU_BF16, EPI_RESID_F32, EPI_DGELU_BF16, EPI_F32 = range(5)
 X3_EPI_F32, X3_EPI_GELU_F32, X3_EPI_RESID_F32 = range(3)     # srhip_gemm_nt_x3
 X3B_NT, X3B_NN = range(2)                                      # srhip_gemm_x3 layouts
 X3B_EPI_F32, X3B_EPI_ACC, X3B_EPI_DGELU, X3B_EPI_GELU_PRE = range(4)  # srhip_gemm_x3 epilogues
+REDUCE_NONE, REDUCE_MEAN, REDUCE_SUM = range(3)               # srhip_ce_hard / ce_soft / consistency_mse / consistency_l1
 
 P, I, F, L, Dbl, U = c_void_p, c_int, c_float, c_long, c_double, c_uint
 SIGNATURES = {
@@ -88,6 +89,10 @@ SIGNATURES = {
     "srhip_softmatch_mask": (I, [P, I, P, P, Dbl, I, P, I, P]),
     "srhip_reward_mask2": (I, [P, P, P, P, I, I, P]),
     "srhip_masked_ce": (I, [P, P, P, P, F, P, P, I, I, P]),
+    "srhip_ce_hard": (I, [P, c_longlong, P, P, P, F, I, P, P, P, c_longlong, I, I, P]),
+    "srhip_ce_soft": (I, [P, c_longlong, P, c_longlong, P, P, F, I, P, P, P, c_longlong, I, I, P]),
+    "srhip_consistency_mse": (I, [P, c_longlong, P, c_longlong, P, P, F, I, P, P, P, c_longlong, I, I, P]),
+    "srhip_consistency_l1": (I, [P, c_longlong, P, c_longlong, P, P, F, I, P, P, P, c_longlong, I, I, P]),
     "srhip_rewarder_param_count": (L, [I, I]),
     "srhip_rewarder_ws_floats": (L, [I, I]),
     "srhip_generator_param_count": (L, [I]),

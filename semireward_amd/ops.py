@@ -8,6 +8,7 @@ from . import _lib
 from ._lib import EPI_BF16, EPI_DGELU_BF16, EPI_F32, EPI_GELU_BF16, EPI_RESID_F32  # noqa: F401
 from ._lib import X3_EPI_F32, X3_EPI_GELU_F32, X3_EPI_RESID_F32  # noqa: F401
 from ._lib import X3B_NT, X3B_NN, X3B_EPI_F32, X3B_EPI_ACC, X3B_EPI_DGELU, X3B_EPI_GELU_PRE  # noqa: F401
+from ._lib import REDUCE_NONE, REDUCE_MEAN, REDUCE_SUM  # noqa: F401
 
 
 # Argument checks cost 0.3 us per pointer x ~4500 pointers per training step = 1.3 ms of host time, which is what bounds the step once the GPU
@@ -816,6 +817,41 @@ def reward_mask2(reward, mask2, mean_out, groups, B, mean_in=None):
 
 def masked_ce(logits, targets, mask, mask2, grad_scale, loss_out, dlogits, B, C):
     _call("srhip_masked_ce", _p(logits), _p(targets), _p(mask), _p(mask2), grad_scale, _p(loss_out), _p(dlogits), B, C, _s())
+
+
+def _rows(t):
+    """(pointer, row stride in elements) of a 2-D device tensor whose rows are dense (a row block or column block of a larger buffer)."""
+    if t is None:
+        return None, 0
+    if _CHECK_ARGS:
+        assert t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.float32, "libsrhip needs fp32 device rows, dense in the last dimension"
+    return t.data_ptr(), t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def ce_hard(logits, targets, mask, mask2, grad_scale, reduction, loss_rows, loss_out, dlogits, B, C):
+    """Hard-target cross entropy with ``reduction`` REDUCE_NONE | REDUCE_MEAN | REDUCE_SUM (criterions.hip); logits / dlogits may be row-strided."""
+    (z, ld), (dl, ldd) = _rows(logits), _rows(dlogits)
+    _call("srhip_ce_hard", z, ld, _p(targets), _p(mask), _p(mask2), grad_scale, reduction, _p(loss_rows), _p(loss_out), dl, ldd, B, C, _s())
+
+
+def _soft_criterion(name, logits, targets, mask, mask2, grad_scale, reduction, loss_rows, loss_out, dlogits, B, C):
+    (z, ld), (t, ldt), (dl, ldd) = _rows(logits), _rows(targets), _rows(dlogits)
+    _call(name, z, ld, t, ldt, _p(mask), _p(mask2), grad_scale, reduction, _p(loss_rows), _p(loss_out), dl, ldd, B, C, _s())
+
+
+def ce_soft(logits, targets, mask, mask2, grad_scale, reduction, loss_rows, loss_out, dlogits, B, C):
+    """Soft-target cross entropy sum_c -t log_softmax(z) (targets fp32 [B, C], not normalised)."""
+    _soft_criterion("srhip_ce_soft", logits, targets, mask, mask2, grad_scale, reduction, loss_rows, loss_out, dlogits, B, C)
+
+
+def consistency_mse(logits, targets, mask, mask2, grad_scale, reduction, loss_rows, loss_out, dlogits, B, C):
+    """mean_c (softmax(z) - t)^2 per row."""
+    _soft_criterion("srhip_consistency_mse", logits, targets, mask, mask2, grad_scale, reduction, loss_rows, loss_out, dlogits, B, C)
+
+
+def consistency_l1(logits, targets, mask, mask2, grad_scale, reduction, loss_rows, loss_out, dlogits, B, C):
+    """mean_c |z - t| per row."""
+    _soft_criterion("srhip_consistency_l1", logits, targets, mask, mask2, grad_scale, reduction, loss_rows, loss_out, dlogits, B, C)
 
 
 # ---- rewarder / generator ---------------------------------------------------------------------
