@@ -624,6 +624,18 @@ int srhip_w2v_pos_finish_bwd(float* dx0, const float* ysave, const float* conv, 
 int srhip_augment(const unsigned char* src, int n_src, int H0, int W0, int B, int S, int pad, const int* ip, const double* dp,
                   unsigned char* scratch, float* out, unsigned char* out_u8, const float* mean3, const float* std3, void* stream);
 
+/* ---- Pillow-exact bilinear resize of a stored uint8 image stack: transforms.Resize(crop_size) on a PIL image, the first op of
+ * transform_weak / transform_strong / transform_val (semilearn/datasets/cv_datasets/eurosat.py:66,76,87, cifar.py:35,43,52,
+ * stl10.py:43,51,60) = Image.resize((S, S), BILINEAR).  src uint8 [N, H0, W0, 3] -> dst uint8 [N, S, S, 3]; square sources only
+ * (H0 != W0: SR_EINVAL).  H0 == S copies the bytes (Pillow skips both passes; the tables may be NULL).  Otherwise
+ *   bounds int32 [S, 2]     : first source index and tap count of output index s (the same table serves both axes),
+ *   coefs  int32 [S, ksize] : the taps' weights in 22-bit fixed point (Pillow's precompute_coeffs + normalize_coeffs_8bpc, computed in
+ *                             float64 on the host: semireward_amd/data/resize.py),
+ *   tmp    uint8 [N, H0, S, 3] scratch for the horizontal pass.
+ * Integer arithmetic only; byte-exact with Pillow 12.2.0 for shrinking (antialiased) and enlarging. */
+int srhip_resize_bilinear_u8(const unsigned char* src, int N, int H0, int W0, unsigned char* dst, int S, const int* bounds, const int* coefs,
+                             int ksize, unsigned char* tmp, void* stream);
+
 /* ---- WideResNet building blocks (classic_cv backbone, semilearn/nets/wrn/wrn.py; BASELINE.json configs[0], parity configuration) ----
  * Feature maps are NHWC = row-major [rows = B*H*W, C].  conv = im2col (bf16) + srhip_gemm_nt; dW = srhip_gemm_tn_grouped_f32(dY, col);
  * dX = srhip_gemm_nt(dY, W^T) + col2im.

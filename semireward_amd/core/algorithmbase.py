@@ -21,7 +21,7 @@ from .. import ops
 from ..distributed import DataParallel
 from ..optim import FusedAdamW, FusedSGD
 from .criterions import CELoss, ConsistencyLoss
-from .hooks import EMAHook, Hook, ParamUpdateHook, TimerHook, get_priority
+from .hooks import DistSamplerSeedHook, EMAHook, Hook, ParamUpdateHook, TimerHook, get_priority
 from .utils import reference_data_functions
 
 
@@ -100,9 +100,13 @@ class AlgorithmBase:
         self.best_eval_metric, self.best_it = 0.0, 0
         self.net_builder = net_builder
         self.ema = None
+        self.device_data = bool(g("device_data", False))     # dataset arrays resident in HBM, loaders of data/device_loader.py
         self.dataset_dict = self.set_dataset()
         self.loader_dict = self.set_data_loader()
         self.model = self.set_model()
+        if self.device_data:
+            from ..data.device_loader import refuse_unsupported_model
+            refuse_unsupported_model(self.model)
         if self.model.couples_batch_rows:
             self.model.dp = self.dp          # BatchNorm backbone under data parallel = SyncBatchNorm, as the reference's send_model_cuda (misc.py:55)
         self.ema_model = self.set_ema_model()
@@ -113,6 +117,8 @@ class AlgorithmBase:
         self._hooks = []
         self.hooks_dict = OrderedDict()
         self.set_hooks()
+        if self.device_data:                  # the reference's DistSamplerSeedHook (algorithmbase.py:565); every other configuration keeps its hook list
+            self.register_hook(DistSamplerSeedHook(), None, "NORMAL")
 
     def init(self, **kwargs):
         raise NotImplementedError
@@ -127,6 +133,9 @@ class AlgorithmBase:
         ready = getattr(a, "dataset_dict", None)
         get_dataset = (getattr(a, "data_functions", None) or reference_data_functions())[0]
         if ready is None and (get_dataset is None or getattr(a, "dataset", None) is None):
+            if self.device_data:
+                raise RuntimeError("device_data: True needs the dataset arrays: pass args.dataset_dict (reference dataset objects, or plain "
+                                   "{'data': uint8 [n, H, W, 3], 'targets': ...} dicts), or install semilearn so that its get_dataset runs")
             return None
         if ready is None:
             if self.rank != 0 and self.distributed:
@@ -135,6 +144,9 @@ class AlgorithmBase:
                                 getattr(a, "include_lb_to_ulb", True))
         if ready is None:
             return None
+        if self.device_data:                  # uint8 arrays -> HBM, resized once to img_size (the transforms' leading Resize)
+            from ..data.device_loader import build_device_datasets
+            ready = build_device_datasets(a, ready, self.device)
         a.ulb_dest_len = len(ready["train_ulb"]) if ready.get("train_ulb") is not None else 0
         a.lb_dest_len = len(ready["train_lb"])
         self.print_fn("unlabeled data number: {}, labeled data number {}".format(a.ulb_dest_len, a.lb_dest_len))
@@ -148,6 +160,13 @@ class AlgorithmBase:
         a = self.args
         if self.dataset_dict is None:
             return getattr(a, "loader_dict", None)
+        if self.device_data:
+            from ..data.device_loader import build_device_loaders
+            self.print_fn("Create device-resident train and test data loaders")
+            ld = build_device_loaders(a, self.dataset_dict, list(signature(self.train_step).parameters), self.num_train_iter, self.epochs,
+                                      self.world_size if self.distributed else 1, self.rank if self.distributed else 0)
+            self.print_fn(f"[!] data loader keys: {ld.keys()}")
+            return ld
         get_data_loader = (getattr(a, "data_functions", None) or reference_data_functions())[1]
         if get_data_loader is None:
             raise RuntimeError("a dataset_dict was given but no get_data_loader: install semilearn or pass args.data_functions")

@@ -121,3 +121,14 @@ class EMAHook(Hook):
 
     def before_run(self, algorithm):
         pass
+
+
+class DistSamplerSeedHook(Hook):
+    """core/hooks/sampler_seed.py of the reference: every epoch reshuffles the train samplers with the epoch as the seed.  Registered only when
+    the device loaders feed the loop (``device_data: True``); they re-seed their augmentation draws with the epoch at the same moment."""
+
+    def before_train_epoch(self, algorithm):
+        for name in ("train_lb", "train_ulb"):
+            loader = (algorithm.loader_dict or {}).get(name)
+            if hasattr(loader, "set_epoch"):
+                loader.set_epoch(algorithm.epoch)

@@ -21,10 +21,9 @@ OPS = ["AutoContrast", "Brightness", "Color", "Contrast", "Equalize", "Identity"
 RANGES = [(0, 1), (0.05, 0.95), (0.05, 0.95), (0.05, 0.95), (0, 1), (0, 1), (4, 8), (-30, 30), (0.05, 0.95), (-0.3, 0.3), (-0.3, 0.3),
           (0, 256), (-0.3, 0.3), (-0.3, 0.3)]
 IPN, DPN, MAX_OPS = 64, 32, 4
-
-
-def _fix(v):
-    return int(math.floor(v * 65536.0 + 0.5))
+_POSTERIZE, _ROTATE, _SHEARX, _SHEARY, _TRANSLATEX, _TRANSLATEY = (OPS.index(n) for n in ("Posterize", "Rotate", "ShearX", "ShearY", "TranslateX",
+                                                                                          "TranslateY"))
+_IS_GEOMETRIC = np.isin(np.arange(len(OPS)), (_ROTATE, _SHEARX, _SHEARY, _TRANSLATEX, _TRANSLATEY))
 
 
 def _affine_matrix(op, v, S):
@@ -50,6 +49,10 @@ class GpuAugment:
         self.rng = np.random.Generator(np.random.PCG64(seed))
         self._scratch = None
 
+    def reseed(self, seed):
+        """Restart the draws: ``seed`` an int or a sequence of ints (the device loaders pass (seed, rank, role, epoch))."""
+        self.rng = np.random.Generator(np.random.PCG64(seed))
+
     def draw(self, B, strong, src_hw=None):
         """The random decisions of one batch: crop offsets in [0, H0 + 2 pad - size], flips, and for strong: op picks, magnitudes, cutout."""
         H0, W0 = src_hw or (self.size, self.size)
@@ -72,27 +75,41 @@ class GpuAugment:
         ip[:, 4] = -1
         ip[:, 8] = np.arange(B) if src_index is None else src_index
         if "ops" in d:
-            n = d["ops"].shape[1]
+            # whole-batch numpy (the loader packs three batches per step); every expression keeps the scalar code's order of float64 operations
+            ops_, vals = np.asarray(d["ops"]).astype(np.int64), np.asarray(d["vals"], dtype=np.float64)
+            n = ops_.shape[1]
             ip[:, 3] = n
-            for b in range(B):
-                for k in range(n):
-                    op, v = int(d["ops"][b, k]), float(d["vals"][b, k])
-                    q, e = ip[b, 16 + 12 * k:], dp[b, 8 * k:]
-                    q[0], e[0] = op, v
-                    if OPS[op] == "Posterize":
-                        q[8] = ~(2 ** (8 - max(1, int(v))) - 1) & 0xFF
-                    elif OPS[op] in ("Rotate", "ShearX", "ShearY", "TranslateX", "TranslateY"):
-                        a = _affine_matrix(op, v, S)
-                        if a[1] == 0 and a[3] == 0:            # Pillow: ImagingScaleAffine (float64 walk)
-                            q[1], e[1], e[2], e[3], e[4] = 1, a[2] + a[0] * 0.5, a[5] + a[4] * 0.5, a[0], a[4]
-                        else:                                  # Pillow: affine_fixed (16.16)
-                            q[2:8] = [_fix(a[0]), _fix(a[1]), _fix(a[2] + a[0] * 0.5 + a[1] * 0.5), _fix(a[3]), _fix(a[4]),
-                                      _fix(a[5] + a[3] * 0.5 + a[4] * 0.5)]
-                cv = float(d["cut_v"][b])                      # Cutout / CutoutAbs (randaugment.py:116-146)
-                if cv > 0.0:
-                    v = cv * S
-                    x0, y0 = int(max(0, float(d["ux"][b]) - v / 2.0)), int(max(0, float(d["uy"][b]) - v / 2.0))
-                    ip[b, 4:8] = [x0, y0, int(min(S, x0 + v)), int(min(S, y0 + v))]
+            q, e = np.zeros((B, n, 12), dtype=np.int64), np.zeros((B, n, 8), dtype=np.float64)
+            q[:, :, 0], e[:, :, 0] = ops_, vals
+            post = ops_ == _POSTERIZE
+            if post.any():
+                q[:, :, 8][post] = ~((1 << (8 - np.maximum(1, vals[post].astype(np.int64)))) - 1) & 0xFF
+            geo = _IS_GEOMETRIC[ops_]
+            if geo.any():
+                one, zero = np.ones((B, n)), np.zeros((B, n))   # the affine matrix a0..a5 of every geometric op
+                a = [one, np.where(ops_ == _SHEARX, vals, zero), np.where(ops_ == _TRANSLATEX, vals * S, zero),
+                     np.where(ops_ == _SHEARY, vals, zero), one, np.where(ops_ == _TRANSLATEY, vals * S, zero)]
+                rot = np.argwhere(ops_ == _ROTATE)
+                if len(rot):                                    # math.cos / math.sin / round(., 15): CPython's, entry by entry
+                    a = [x.copy() for x in a]
+                    for r, k in rot:
+                        m = _affine_matrix(_ROTATE, float(vals[r, k]), S)
+                        for c in range(6):
+                            a[c][r, k] = m[c]
+                walk = geo & (a[1] == 0) & (a[3] == 0)          # Pillow: ImagingScaleAffine (float64 walk); else affine_fixed (16.16)
+                q[:, :, 1] = walk
+                e[:, :, 1:5] = np.where(walk[:, :, None], np.stack([a[2] + a[0] * 0.5, a[5] + a[4] * 0.5, a[0], a[4]], axis=2), 0.0)
+                fx = np.stack([a[0], a[1], a[2] + a[0] * 0.5 + a[1] * 0.5, a[3], a[4], a[5] + a[3] * 0.5 + a[4] * 0.5], axis=2)
+                q[:, :, 2:8] = np.where((geo & ~walk)[:, :, None], np.floor(fx * 65536.0 + 0.5), 0.0)
+                if np.abs(q[:, :, 2:8]).max() > 0x7FFFFFFF:    # (the int32 block would wrap; the magnitudes of RANGES stay far below)
+                    raise OverflowError("affine coefficient outside the 16.16 fixed-point range")
+            ip[:, 16:16 + 12 * n], dp[:, :8 * n] = q.reshape(B, 12 * n), e.reshape(B, 8 * n)
+            cv = np.asarray(d["cut_v"], dtype=np.float64)      # Cutout / CutoutAbs (randaugment.py:116-146)
+            v = cv * S
+            x0 = np.maximum(0.0, np.asarray(d["ux"], dtype=np.float64) - v / 2.0).astype(np.int64)
+            y0 = np.maximum(0.0, np.asarray(d["uy"], dtype=np.float64) - v / 2.0).astype(np.int64)
+            cut = np.stack([x0, y0, np.minimum(float(S), x0 + v).astype(np.int64), np.minimum(float(S), y0 + v).astype(np.int64)], axis=1)
+            ip[:, 4:8][cv > 0.0] = cut[cv > 0.0]
         return ip, dp
 
     def __call__(self, src_u8, strong, draws=None, src_index=None, return_u8=False):

@@ -1338,3 +1338,31 @@ def make_group_tn_desc_ld(problems, device, tile=128):
     nbytes = float(sum(2.0 * (M * K + N * K) + 8.0 * M * N for *_, M, N, K in problems))
     return torch.from_numpy(arr.view(np.uint8).copy()).to(device), len(problems), t, flops, nbytes
 
+
+_RESIZE_TABLES = {}
+
+
+def resize_bilinear_u8(src, S, chunk=4096):
+    """uint8 [N, H0, H0, 3] device tensor -> new uint8 [N, S, S, 3]: Image.resize((S, S), BILINEAR) of Pillow, byte for byte (srhip.h).  The
+    host tables of (H0, S) are built once and kept on the device; ``chunk`` images per launch bound the horizontal pass's scratch."""
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[-1] != 3:
+        raise ValueError("resize_bilinear_u8 takes uint8 [N, H, W, 3] images, got %s %s" % (src.dtype, tuple(src.shape)))
+    N, H0, W0, _ = src.shape
+    if H0 != W0:
+        raise ValueError("resize_bilinear_u8: square images only (the four SemiReward cv datasets are), got %d x %d" % (H0, W0))
+    assert src.is_cuda and src.is_contiguous() and N > 0 and S > 0
+    dst = torch.empty(N, S, S, 3, dtype=torch.uint8, device=src.device)
+    if H0 == S:
+        _call("srhip_resize_bilinear_u8", _p(src), N, H0, W0, _p(dst), S, None, None, 0, None, _s())
+        return dst
+    key = (H0, S, src.device)
+    if key not in _RESIZE_TABLES:
+        from .data.resize import resize_tables
+        b, c, k = resize_tables(H0, S)
+        _RESIZE_TABLES[key] = (torch.from_numpy(b).to(src.device), torch.from_numpy(c).to(src.device), k)
+    bounds, coefs, ksize = _RESIZE_TABLES[key]
+    tmp = torch.empty(min(N, chunk) * H0 * S * 3, dtype=torch.uint8, device=src.device)
+    for s in range(0, N, chunk):
+        n = min(chunk, N - s)
+        _call("srhip_resize_bilinear_u8", _p(src[s:s + n]), n, H0, W0, _p(dst[s:s + n]), S, _p(bounds), _p(coefs), ksize, _p(tmp), _s())
+    return dst
