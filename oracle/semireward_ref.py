@@ -49,33 +49,55 @@ def generator_shapes(feature_dim):
     return out
 
 
-def _ln(x, w, b, eps=1e-5):
+def _ln_parts(x, w, b, eps=1e-5):
+    """(LayerNorm(x), xhat, rstd): the normalised rows before the affine map and 1 / sqrt(var + eps) per row."""
     mu = x.mean(dim=-1, keepdim=True)
     var = ((x - mu) ** 2).mean(dim=-1, keepdim=True)
-    return (x - mu) / torch.sqrt(var + eps) * w + b
+    xhat = (x - mu) / torch.sqrt(var + eps)
+    return xhat * w + b, xhat, 1.0 / torch.sqrt(var + eps).squeeze(-1)
 
 
-def rewarder_forward(p, features, labels):
-    """semireward.py:52-72 (SURVEY Appendix D).  features [B,F] f32, labels [B] i64 -> [B,1]."""
-    h = _ln(features @ p["feature_fc.weight"].t() + p["feature_fc.bias"],
-            p["feature_norm.weight"], p["feature_norm.bias"])
-    e = _ln(p["label_embedding.weight"][labels], p["label_norm.weight"], p["label_norm.bias"])
+def _ln(x, w, b, eps=1e-5):
+    return _ln_parts(x, w, b, eps)[0]
+
+
+def rewarder_intermediates(p, features, labels):
+    """Every stage of ``rewarder_forward`` by name, in the dtype of the inputs: h, e [B,128]; z, xhat [2B,128] and rstd [2B] (feature rows
+    first, then label rows); logits, alpha [2B]; ctx [128]; u, m2 [B,128]; m1_pre, m1 [B,256]; f1_pre, f1 [B,64] (the ``_pre`` tensors are
+    the ReLU inputs); reward [B,1]."""
+    h, xh_f, rs_f = _ln_parts(features @ p["feature_fc.weight"].t() + p["feature_fc.bias"],
+                              p["feature_norm.weight"], p["feature_norm.bias"])
+    e, xh_l, rs_l = _ln_parts(p["label_embedding.weight"][labels], p["label_norm.weight"], p["label_norm.bias"])
     z = torch.cat((h, e), dim=0)                                   # [2B,128]
     s = z @ p["cross_attention_fc.weight"].t() + p["cross_attention_fc.bias"]  # [2B,1]
     a = torch.softmax(s, dim=0)                                    # over the BATCH rows (:61)
     c = (a * z).sum(dim=0)                                         # [128]
     u = c.unsqueeze(0) + e
-    m1 = torch.relu(u @ p["mlp_fc1.weight"].t() + p["mlp_fc1.bias"])
+    m1_pre = u @ p["mlp_fc1.weight"].t() + p["mlp_fc1.bias"]
+    m1 = torch.relu(m1_pre)
     m2 = m1 @ p["mlp_fc2.weight"].t() + p["mlp_fc2.bias"]
-    f1 = torch.relu(m2 @ p["ffn_fc1.weight"].t() + p["ffn_fc1.bias"])
-    return torch.sigmoid(f1 @ p["ffn_fc2.weight"].t() + p["ffn_fc2.bias"])
+    f1_pre = m2 @ p["ffn_fc1.weight"].t() + p["ffn_fc1.bias"]
+    f1 = torch.relu(f1_pre)
+    reward = torch.sigmoid(f1 @ p["ffn_fc2.weight"].t() + p["ffn_fc2.bias"])
+    return dict(h=h, e=e, z=z, xhat=torch.cat((xh_f, xh_l), dim=0), rstd=torch.cat((rs_f, rs_l), dim=0), logits=s.squeeze(1),
+                alpha=a.squeeze(1), ctx=c, u=u, m1_pre=m1_pre, m1=m1, m2=m2, f1_pre=f1_pre, f1=f1, reward=reward)
+
+
+def rewarder_forward(p, features, labels):
+    """semireward.py:52-72 (SURVEY Appendix D).  features [B,F] f32, labels [B] i64 -> [B,1]."""
+    return rewarder_intermediates(p, features, labels)["reward"]
+
+
+def generator_last_preact(p, x):
+    """Input of the generator's last ReLU, [B,1]: ``generator_forward`` is its ``relu``."""
+    for i in (0, 2, 4):
+        x = torch.relu(x @ p[f"fc_layers.{i}.weight"].t() + p[f"fc_layers.{i}.bias"])
+    return x @ p["fc_layers.6.weight"].t() + p["fc_layers.6.bias"]
 
 
 def generator_forward(p, x):
     """semireward.py:21-24: F->256->128->64->1, ReLU after every layer (incl. the last)."""
-    for i in (0, 2, 4, 6):
-        x = torch.relu(x @ p[f"fc_layers.{i}.weight"].t() + p[f"fc_layers.{i}.bias"])
-    return x
+    return torch.relu(generator_last_preact(p, x))
 
 
 def generated_labels(p, x):
