@@ -170,6 +170,23 @@ int srhip_layernorm_bwd_part(const void* dy, const float* x, const float* mean, 
                              int n_rep, void* out_bf16, const float* row_scale, int rows_per_sample, int M, int D, void* stream);
 typedef struct srhip_ln_reduce_desc { float* dgamma; float* dbeta; } srhip_ln_reduce_desc;   /* 16 bytes */
 int srhip_ln_grad_reduce(const srhip_ln_reduce_desc* desc_dev, float* part, int n_ln, int n_rep, int D, void* stream);
+/* srhip_gemm_tn_grouped_f32 with the ViT backward's small sums over all rows as extra workgroups behind its tiles (one launch instead of five;
+ * the small workgroups fill the slots the last round of tiles leaves empty).  The tail (a HOST struct, passed by value to the kernel) names
+ *   - srhip_ln_grad_reduce(ln_desc, ln_part, n_ln, n_rep, D)                                   (n_ln = 0: none),
+ *   - the dWh / dbh half of srhip_cls_head_bwd(dlogits [B,C], feat [B,D])                       (C = 0: none),
+ *   - the dpos / dcls launch and stage 1 (partial sums into pe_ws) of srhip_patch_embed_bwd_ws  (dx = NULL: none); stage 2 reads what stage 1
+ *     wrote and stays a launch behind this one: srhip_patch_embed_bwd_fold.
+ * Every element is summed by one thread in the order of the separate launches: same bits.  None of the tail's outputs may alias a C / dbias of
+ * the table. */
+typedef struct srhip_dw_tail {
+  const srhip_ln_reduce_desc* ln_desc; float* ln_part;
+  const float* dlogits; const float* feat; float* dWh; float* dbh;
+  const float* dx; const float* img; const int* img_index; float* dpos; float* dcls; float* pe_ws;
+  int n_ln, n_rep, C, B, D, in_chans, HW, ps;
+} srhip_dw_tail;                         /* 128 bytes */
+int srhip_gemm_tn_grouped_tail_f32(const srhip_group_tn_desc* desc_dev, int n_problems, int total_tiles, float alpha, float beta,
+                                   const srhip_dw_tail* tail, void* stream);
+int srhip_patch_embed_bwd_fold(const float* ws, float* dWp, float* dbp, int B, int C, int HW, int ps, int D, void* stream);
 
 /* Fused MLP half of a transformer block on the fp32 residual stream (x -> x_out, both [M, D]; x_out may equal x):
  *   x_out = x + row_scale[m / rows_per_sample] * ( fc2( GELU( fc1( LayerNorm(x) ) ) ) + b2 )

@@ -32,6 +32,8 @@ SIGNATURES = {
     "srhip_gemm_nt_grouped_n64_f32": (I, [P, I, I, F, F, P]),
     "srhip_gemm_tn_grouped_f32": (I, [P, I, I, F, F, P]),
     "srhip_gemm_tn_grouped_pp_f32": (I, [P, I, I, F, F, P]),
+    "srhip_gemm_tn_grouped_tail_f32": (I, [P, I, I, F, F, P, P]),
+    "srhip_patch_embed_bwd_fold": (I, [P, P, P, I, I, I, I, I, P]),
     "srhip_slab_reduce_f32": (I, [P, I, I, P]),
     "srhip_attn_fwd": (I, [P, P, P, I, I, I, F, P]),
     "srhip_attn_bwd": (I, [P, P, P, P, P, P, I, I, I, F, P]),
@@ -178,6 +180,12 @@ SIGNATURES = {
 }
 
 _lib = None
+
+
+class DwTail(ctypes.Structure):
+    """srhip_dw_tail (include/srhip.h): the small launches that ride behind the tiles of srhip_gemm_tn_grouped_tail_f32."""
+    _fields_ = [(n, c_void_p) for n in ("ln_desc", "ln_part", "dlogits", "feat", "dWh", "dbh", "dx", "img", "img_index", "dpos", "dcls",
+                                         "pe_ws")] + [(n, c_int) for n in ("n_ln", "n_rep", "C", "B", "D", "in_chans", "HW", "ps")]
 
 
 def lib():

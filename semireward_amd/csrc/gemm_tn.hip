@@ -21,6 +21,7 @@
 
 #include "../../include/srhip.h"
 #include "common.h"
+#include "tail_ops.h"
 
 namespace {
 
@@ -39,10 +40,9 @@ __device__ __forceinline__ u32x2_t ds_read_tr16(const bf16_t* p) {
   return __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p));
 }
 
-__global__ __launch_bounds__(256, 3) void gemm_tn_grouped_f32_kernel(const srhip_group_tn_desc* __restrict__ desc, int n_problems,
-                                                                     float alpha, float beta) {
-  __shared__ __attribute__((aligned(16))) bf16_t smem[NS * STAGE];
-  const int tile = xcd_remap(blockIdx.x, gridDim.x);
+// one 128 x 128 output tile (tile < the table's total) by the 256 threads of a workgroup; smem: NS * STAGE bf16
+__device__ __forceinline__ void gemm_tn_tile_body(const srhip_group_tn_desc* __restrict__ desc, int n_problems, float alpha, float beta,
+                                                  const int tile, bf16_t* smem) {
   int p = 0;
   {  // binary search: the last entry whose tile_start <= tile (a token-sliced table has hundreds of entries; a linear walk of dependent scalar
      // loads cost a workgroup as much as its product)
@@ -162,6 +162,40 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_grouped_f32_kernel(const srhip
       *cp = x;
     }
   }
+}
+
+__global__ __launch_bounds__(256, 3) void gemm_tn_grouped_f32_kernel(const srhip_group_tn_desc* __restrict__ desc, int n_problems,
+                                                                     float alpha, float beta) {
+  __shared__ __attribute__((aligned(16))) bf16_t smem[NS * STAGE];
+  gemm_tn_tile_body(desc, n_problems, alpha, beta, xcd_remap(blockIdx.x, gridDim.x), smem);
+}
+
+// The same launch with the backward's small "sums over all rows" behind its tiles: workgroups [0, gemm_tiles) are the table's tiles, the ones
+// after them run the bodies of tail_ops.h in the order LayerNorm copies | head classes | tokens (dpos) | patch-embed chunks.  The hardware
+// hands workgroups out in index order, so the small ones start as the last round of tiles drains -- on slots that a table of 1296 tiles leaves
+// empty (768 resident slots: the second round is 528) -- instead of one latency-bound launch after another around the product.  Nothing a
+// tail workgroup writes is read or written by a tile (LayerNorm / head / pos_embed / cls_token gradients and the patch-embed workspace against
+// the blocks' weight and bias gradients), so no ordering between them is needed.
+__global__ __launch_bounds__(256, 3) void gemm_tn_grouped_tail_f32_kernel(const srhip_group_tn_desc* __restrict__ desc, int n_problems,
+                                                                          int gemm_tiles, float alpha, float beta, const srhip_dw_tail t) {
+  __shared__ __attribute__((aligned(16))) bf16_t smem[NS * STAGE];
+  if ((int)blockIdx.x < gemm_tiles) {
+    gemm_tn_tile_body(desc, n_problems, alpha, beta, xcd_remap(blockIdx.x, gemm_tiles), smem);
+    return;
+  }
+  int b = blockIdx.x - gemm_tiles;
+  const int tid = threadIdx.x;
+  const int nlx = (2 * t.D + 255) / 256, nln = nlx * t.n_ln;
+  if (b < nln) { ln_grad_reduce_body(t.ln_desc, t.ln_part, t.n_rep, t.D, b % nlx, b / nlx, tid); return; }
+  b -= nln;
+  if (b < t.C) { cls_head_bwd_w_body(t.dlogits, t.feat, t.dWh, t.dbh, t.B, t.D, t.C, b, tid); return; }
+  b -= t.C;
+  if (!t.dx) return;
+  const int gw = t.HW / t.ps, N = gw * gw + 1, nch = (N - 1 + PE_TOK - 1) / PE_TOK;
+  if (b < N) { pe_bwd_pos_body(t.dx, t.dpos, t.dcls, t.B, N, t.D, b, tid, 256); return; }
+  b -= N;
+  if (b < nch * t.B)
+    pe_bwd_part_body(t.dx, t.img, t.img_index, t.pe_ws, t.in_chans, t.HW, t.ps, t.D, reinterpret_cast<float*>(smem), b % nch, b / nch, nch, tid, 256);
 }
 
 
@@ -489,6 +523,27 @@ extern "C" int srhip_gemm_tn_grouped_pp_f32(const srhip_group_tn_desc* desc_dev,
   constexpr size_t sm = (size_t)PSLOT * PH_EL * sizeof(bf16_t);
   (void)hipFuncSetAttribute((const void*)gemm_tn_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   SR_LAUNCH(gemm_tn_pp_kernel, dim3(min(total_tiles, 256)), dim3(512), sm, (hipStream_t)stream, desc_dev, n_problems, total_tiles, alpha, beta);
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+
+extern "C" int srhip_gemm_tn_grouped_tail_f32(const srhip_group_tn_desc* desc_dev, int n_problems, int total_tiles, float alpha, float beta,
+                                              const srhip_dw_tail* tail, void* stream) {
+  if (!desc_dev || n_problems <= 0 || n_problems > 4096 || total_tiles <= 0 || !tail) return SR_EINVAL;
+  const srhip_dw_tail t = *tail;
+  if (t.D <= 0 || t.n_ln < 0 || t.C < 0 || (t.n_ln > 0 && (!t.ln_desc || !t.ln_part || t.n_rep <= 0))) return SR_EINVAL;
+  if (t.C > 0 && (t.B <= 0 || !t.dlogits || !t.feat || !t.dWh || !t.dbh)) return SR_EINVAL;
+  long extra = (long)cdiv(2 * t.D, 256) * t.n_ln + t.C;
+  if (t.dx) {      // the small-patch embedding only (the shapes srhip_patch_embed_bwd_ws takes): its LDS patch lies in the tiles' stages
+    if (t.B <= 0 || t.in_chans <= 0 || t.ps <= 0 || t.HW <= 0 || t.HW % t.ps != 0 || t.D % 64 != 0 || t.D > 1024 ||
+        t.in_chans * t.ps * t.ps > 64 || !t.img || !t.dpos || !t.dcls || !t.pe_ws)
+      return SR_EINVAL;
+    const int gw = t.HW / t.ps, N = gw * gw + 1;
+    extra += N + (long)cdiv(N - 1, PE_TOK) * t.B;
+  }
+  if (total_tiles + extra > 0x7fffffffL) return SR_EINVAL;
+  SR_LAUNCH(gemm_tn_grouped_tail_f32_kernel, dim3((unsigned)(total_tiles + extra)), dim3(256), 0, (hipStream_t)stream, desc_dev, n_problems,
+                     total_tiles, alpha, beta, t);
   SR_CHECK_LAUNCH();
   return SR_OK;
 }

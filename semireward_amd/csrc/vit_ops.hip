@@ -11,6 +11,7 @@
 // (fp32 residual stream -> bf16 GEMM operand) into the producing kernel.
 #include "common.h"
 #include "srhip.h"
+#include "tail_ops.h"
 
 namespace {
 
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDY* __restrict__ dy,
 // ---------------------------------------------------------------------------------------------
 // Patch embedding (small patches: K = C*p*p <= 48 is an HBM-bound VALU op, not a GEMM).
 // x[b, 0, :] = cls + pos[0];  x[b, 1+p, :] = patch(b,p) . Wp^T + bp + pos[1+p].   blockDim = D.
-constexpr int PE_TOK = 32;
+// (PE_TOK tokens per workgroup: tail_ops.h)
 __global__ void patch_embed_fwd_kernel(const float* __restrict__ img, const int* __restrict__ img_index,
                                        const float* __restrict__ Wp, const float* __restrict__ bp,
                                        const float* __restrict__ cls, const float* __restrict__ pos,
@@ -226,42 +227,7 @@ __global__ void patch_embed_fwd_kernel(const float* __restrict__ img, const int*
 __global__ void patch_embed_bwd_part_kernel(const float* __restrict__ dx, const float* __restrict__ img, const int* __restrict__ img_index,
                                             float* __restrict__ ws, int C, int HW, int ps, int D) {
   extern __shared__ __attribute__((aligned(16))) float patch[];     // [PE_TOK][K]
-  const int gw = HW / ps, N = gw * gw + 1, K = C * ps * ps;
-  const int b = blockIdx.y, t0 = 1 + blockIdx.x * PE_TOK, d = threadIdx.x;
-  const int bi = img_index ? img_index[b] : b;
-  const float* im = img + (size_t)bi * C * HW * HW;
-  const int nt = min(PE_TOK, N - t0);
-  for (int e = threadIdx.x; e < nt * K; e += blockDim.x) {
-    const int tt = e / K, k = e % K, p = t0 + tt - 1, py = p / gw, px = p % gw;
-    const int c = k / (ps * ps), i = (k / ps) % ps, j = k % ps;
-    patch[e] = im[((size_t)c * HW + py * ps + i) * HW + px * ps + j];
-  }
-  __syncthreads();
-  const float* g0 = dx + ((size_t)b * N + t0) * D + d;
-  float* out = ws + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * (K + 1) * D + d;
-  float accb = 0.f;
-  for (int k0 = 0; k0 < K; k0 += 16) {         // K is small; register-block 16 taps at a time
-    float acc[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) acc[k] = 0.f;
-    for (int tb = 0; tb < nt; tb += 8) {       // 8 gradient rows in flight (the loop is otherwise a chain of L2 round trips)
-      float g[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) g[i] = (tb + i < nt) ? g0[(size_t)(tb + i) * D] : 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int tt = min(tb + i, nt - 1);
-        if (k0 == 0) accb += g[i];
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-          if (k0 + k < K) acc[k] += g[i] * patch[tt * K + k0 + k];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k0 + k < K) out[(size_t)(k0 + k) * D] = acc[k];
-  }
-  out[(size_t)K * D] = accb;
+  pe_bwd_part_body(dx, img, img_index, ws, C, HW, ps, D, patch, blockIdx.x, blockIdx.y, gridDim.x, threadIdx.x, blockDim.x);
 }
 __global__ __launch_bounds__(256) void patch_embed_bwd_fold_kernel(const float* __restrict__ ws, float* __restrict__ dWp, float* __restrict__ dbp,
                                                                   int n_wg, int K, int D) {
@@ -277,11 +243,7 @@ __global__ __launch_bounds__(256) void patch_embed_bwd_fold_kernel(const float* 
 // dpos[t,d] += sum_b dx[b,t,d]; dcls[d] += sum_b dx[b,0,d].  grid = N, block = D.
 __global__ void patch_embed_bwd_pos_kernel(const float* __restrict__ dx, float* __restrict__ dpos, float* __restrict__ dcls,
                                            int B, int N, int D) {
-  const int t = blockIdx.x, d = threadIdx.x;
-  float s = 0.f;
-  for (int b = 0; b < B; ++b) s += dx[((size_t)b * N + t) * D + d];
-  dpos[(size_t)t * D + d] += s;
-  if (t == 0) dcls[d] += s;
+  pe_bwd_pos_body(dx, dpos, dcls, B, N, D, blockIdx.x, threadIdx.x, blockDim.x);
 }
 
 // dWp[d,k] += sum_{b,p} dx[b,1+p,d] * patch[b,p,k]; dbp[d] += sum dx.   grid = (chunks, B), block = D.
@@ -438,17 +400,7 @@ __global__ __launch_bounds__(256) void cls_head_bwd_x_kernel(const float* __rest
 // backward B: grid = C.  dWh[c,:] += sum_b dlogits[b,c] * feat[b,:]; dbh[c] += sum_b dlogits[b,c]
 __global__ __launch_bounds__(256) void cls_head_bwd_w_kernel(const float* __restrict__ dlogits, const float* __restrict__ feat,
                                                             float* __restrict__ dWh, float* __restrict__ dbh, int B, int D, int C) {
-  const int c = blockIdx.x;
-  for (int d = threadIdx.x; d < D; d += 256) {
-    float a = 0.f;
-    for (int b = 0; b < B; ++b) a += dlogits[(size_t)b * C + c] * feat[(size_t)b * D + d];
-    dWh[(size_t)c * D + d] += a;
-  }
-  if (threadIdx.x == 0) {
-    float a = 0.f;
-    for (int b = 0; b < B; ++b) a += dlogits[(size_t)b * C + c];
-    dbh[c] += a;
-  }
+  cls_head_bwd_w_body(dlogits, feat, dWh, dbh, B, D, C, blockIdx.x, threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -669,14 +621,7 @@ namespace {
 // dgamma / dbeta of n_ln LayerNorms += the sum of their n_rep partial copies ([n_ln][n_rep][2][D]); the copies are cleared for the next step.
 __global__ __launch_bounds__(256) void ln_grad_reduce_kernel(const srhip_ln_reduce_desc* __restrict__ desc, float* __restrict__ part, int n_rep,
                                                             int D) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= 2 * D) return;
-  float* p = part + (size_t)blockIdx.y * n_rep * 2 * D + c;
-  float acc = 0.f;
-  for (int r = 0; r < n_rep; ++r) { acc += p[(size_t)r * 2 * D]; p[(size_t)r * 2 * D] = 0.f; }
-  const srhip_ln_reduce_desc d = desc[blockIdx.y];
-  float* dst = c < D ? d.dgamma + c : d.dbeta + (c - D);
-  *dst += acc;
+  ln_grad_reduce_body(desc, part, n_rep, D, blockIdx.x, blockIdx.y, threadIdx.x);
 }
 }  // namespace
 extern "C" int srhip_ln_grad_reduce(const srhip_ln_reduce_desc* desc_dev, float* part, int n_ln, int n_rep, int D, void* stream) {
@@ -730,6 +675,15 @@ extern "C" int srhip_patch_embed_bwd_ws(const float* dx, const float* img, const
   SR_LAUNCH(patch_embed_bwd_part_kernel, dim3(nch, B), dim3(D), PE_TOK * K * sizeof(float), s, dx, img, img_index, ws, C, HW, ps, D);
   SR_CHECK_LAUNCH();
   SR_LAUNCH(patch_embed_bwd_fold_kernel, dim3(cdiv((K + 1) * D, 256)), dim3(256), 0, s, ws, dWp, dbp, nch * B, K, D);
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+
+// stage 2 alone: the workgroups of stage 1 ran behind the tiles of srhip_gemm_tn_grouped_tail_f32
+extern "C" int srhip_patch_embed_bwd_fold(const float* ws, float* dWp, float* dbp, int B, int C, int HW, int ps, int D, void* stream) {
+  if (!pe_shape_ok(B, C, HW, ps, D) || !ws || !dWp || !dbp) return SR_EINVAL;
+  const int gw = HW / ps, K = C * ps * ps, nch = cdiv(gw * gw, PE_TOK);
+  SR_LAUNCH(patch_embed_bwd_fold_kernel, dim3(cdiv((K + 1) * D, 256)), dim3(256), 0, (hipStream_t)stream, ws, dWp, dbp, nch * B, K, D);
   SR_CHECK_LAUNCH();
   return SR_OK;
 }

@@ -684,20 +684,33 @@ class VisionTransformer(ModuleSurface):
         G = lambda n: self.p(n, self.grad)   # noqa: E731
         T = self._bwd_plan(M, ctx)
         dx = self._buf("b_dx", (M, D), f32)
-        ops.cls_head_bwd(dlogits, None, None, ctx.feat, None, None, None, G("head.weight"), G("head.bias"), None, None, B, N, D, C)
-        if not getattr(self, "_groups_launched", False):      # (a partial-range chain never launches them, whether or not a callback is installed)
-            ops.ln_grad_reduce(T["ln_desc"], T["ln_part"], 2 * cfg.depth, LN_REP, D)
-            desc, npb, ntiles, flops, nbytes = T["desc"]
-            ops.gemm_tn_grouped_f32(desc, npb, ntiles, alpha=1.0, beta=1.0, flops=flops, nbytes=nbytes)
-            if self.grad_ready_cb is not None:
-                lo = min(g["flat"][0] for g in T["groups"]); hi = max(g["flat"][1] for g in T["groups"])
-                self.grad_ready_cb(lo, hi)              # the blocks' range in one piece (the chain did not hand it over in groups)
-        self._groups_launched = False
         Kp = cfg.in_chans * cfg.patch_size ** 2
-        if Kp <= 64:
-            ws = self._buf("b_pe_ws", (ops.patch_embed_bwd_ws_floats(B, cfg.in_chans, cfg.img_size, cfg.patch_size, D),), f32)
+        small_pe = Kp <= 64                                 # the two-stage patch-embedding kernels (one thread per feature, the patch in LDS)
+        ws = self._buf("b_pe_ws", (ops.patch_embed_bwd_ws_floats(B, cfg.in_chans, cfg.img_size, cfg.patch_size, D),), f32) if small_pe else None
+        groups_launched = getattr(self, "_groups_launched", False)    # (a partial-range chain never launches them, callback or not)
+        # One launch for the blocks' weight gradients AND the small sums over all rows (head weight, LayerNorm copies, dpos / dcls, stage 1 of the
+        # patch-embedding gradient): they ran as latency-bound launches around the product, on the step's own stream with nothing beside them;
+        # as extra workgroups they fill the slots the product's last round of tiles leaves empty.  (Not under the per-launch profiler, which times
+        # the product alone -- DESIGN.md section 7 -- nor for a table with a slab phase.)
+        merged = not groups_launched and ops._PROFILE is None and getattr(T["desc"][0], "reduce", None) is None
+        desc, npb, ntiles, flops, nbytes = T["desc"]
+        if merged:
+            pe = (dx, ctx.img, ctx.img_index, G("pos_embed"), G("cls_token"), ws, B, cfg.in_chans, cfg.img_size, cfg.patch_size) if small_pe else None
+            ops.gemm_tn_grouped_tail_f32(desc, npb, ntiles, D, ln=(T["ln_desc"], T["ln_part"], 2 * cfg.depth, LN_REP),
+                                         head=(dlogits, ctx.feat, G("head.weight"), G("head.bias"), B, C), pe=pe)
+        else:
+            ops.cls_head_bwd(dlogits, None, None, ctx.feat, None, None, None, G("head.weight"), G("head.bias"), None, None, B, N, D, C)
+            if not groups_launched:
+                ops.ln_grad_reduce(T["ln_desc"], T["ln_part"], 2 * cfg.depth, LN_REP, D)
+                ops.gemm_tn_grouped_f32(desc, npb, ntiles, alpha=1.0, beta=1.0, flops=flops, nbytes=nbytes)
+        if not groups_launched and self.grad_ready_cb is not None:
+            lo = min(g["flat"][0] for g in T["groups"]); hi = max(g["flat"][1] for g in T["groups"])
+            self.grad_ready_cb(lo, hi)                  # the blocks' range in one piece (the chain did not hand it over in groups)
+        self._groups_launched = False
+        if small_pe:
+            part_done = merged                          # dpos / dcls and stage 1 rode in the merged launch: only the fold is left
             ops.patch_embed_bwd_ws(dx, ctx.img, ctx.img_index, G("patch_embed.proj.weight"), G("patch_embed.proj.bias"), G("cls_token"),
-                                   G("pos_embed"), ws, B, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
+                                   G("pos_embed"), ws, B, cfg.in_chans, cfg.img_size, cfg.patch_size, D, part_done)
         else:                                       # dWp += dx_tok^T col, dbp += colsum dx_tok (TN grouped GEMM, one problem); dpos, dcls
             Np = N - 1
             key = ("pebwd", B)

@@ -1,5 +1,6 @@
 """Torch-tensor front end of the C ABI (include/srhip.h).  Torch is plumbing only: it owns device
 memory and the stream; every op below is a hand-written HIP kernel in libsrhip.so.  No fallbacks."""
+import ctypes
 import os
 
 import torch
@@ -393,6 +394,8 @@ def make_group_tn_desc(problems, device, split_k=0, tile=128, slabs=False, stage
     nbytes = float(sum(2.0 * (M * K + N * K) + 8.0 * M * N for *_, M, N, K in problems))
     up = (lambda a: stager.upload(a.view(np.uint8).reshape(-1), device)) if stager is not None else (lambda a: torch.from_numpy(a.view(np.uint8).copy()).to(device))
     desc = up(arr)
+    # host copy of what the table writes, as (first byte, bytes): gemm_tn_grouped_tail_f32 checks its tail's outputs against it
+    desc.out_ranges = [(e[2], 4 * e[4] * e[5]) for e in ent] + [(e[3], 4 * e[4]) for e in ent if e[3]]
     if slabs:
         ra = np.zeros(len(red), dtype=SLAB_DESC_DTYPE)
         for i, e in enumerate(red):
@@ -451,6 +454,32 @@ def gemm_tn_grouped_f32(desc, n_problems, total_tiles, alpha=1.0, beta=1.0, flop
         _call(fn, _p(desc), n_problems, total_tiles, alpha, beta, _s())
     if red is not None:
         _call("srhip_slab_reduce_f32", _p(red[0]), red[1], red[2], _s())
+
+
+def gemm_tn_grouped_tail_f32(desc, n_problems, total_tiles, D, ln=None, head=None, pe=None, alpha=1.0, beta=1.0):
+    """gemm_tn_grouped_f32 with the ViT backward's small sums over all rows as extra workgroups of the same launch (srhip_dw_tail):
+    ln = (desc, part, n_ln, n_rep): ln_grad_reduce;  head = (dlogits, feat, dWh, dbh, B, C): the weight half of cls_head_bwd;
+    pe = (dx, img, img_index, dpos, dcls, ws, B, in_chans, HW, ps): the dpos / dcls launch and stage 1 of patch_embed_bwd_ws --
+    patch_embed_bwd_ws(..., part_done=True) must follow.  Same bits as the separate launches."""
+    from ._lib import DwTail
+    assert getattr(desc, "reduce", None) is None, "a table with slab slices has a second phase of its own"
+    t = DwTail()
+    t.D = D
+    if ln is not None:
+        t.ln_desc, t.ln_part, t.n_ln, t.n_rep = _p(ln[0]), _p(ln[1]), ln[2], ln[3]
+    if head is not None:
+        t.dlogits, t.feat, t.dWh, t.dbh, t.B, t.C = _p(head[0]), _p(head[1]), _p(head[2]), _p(head[3]), head[4], head[5]
+    if pe is not None:
+        assert head is None or head[4] == pe[6]
+        t.dx, t.img, t.img_index, t.dpos, t.dcls, t.pe_ws = (_p(x) for x in pe[:6])
+        t.B, t.in_chans, t.HW, t.ps = pe[6:]
+    if _CHECK_ARGS:     # the tail's workgroups run beside the tiles: nothing they write may be written by a tile (srhip.h)
+        mine = list(getattr(ln[0], "out_ranges", ())) if ln is not None else []
+        mine += [(_p(x), x.numel() * x.element_size()) for x in ((head[2], head[3]) if head is not None else ()) + (tuple(pe[3:6]) if pe is not None else ())]
+        for a0, an in mine:
+            for b0, bn in getattr(desc, "out_ranges", ()):
+                assert a0 + an <= b0 or b0 + bn <= a0, "a tail output of gemm_tn_grouped_tail_f32 overlaps a C / dbias of the table"
+    _call("srhip_gemm_tn_grouped_tail_f32", _p(desc), n_problems, total_tiles, alpha, beta, ctypes.addressof(t), _s())
 
 
 def attn_block_supported(N, D, H):
@@ -513,7 +542,9 @@ def make_ln_reduce_desc(pairs, device):
     """pairs: list of (dgamma, dbeta) fp32 views of the gradient block, in the order of the partial copies."""
     import numpy as np
     arr = np.array([[_p(g), _p(b)] for g, b in pairs], dtype=np.uint64)
-    return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+    desc = torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+    desc.out_ranges = [(_p(t), t.numel() * t.element_size()) for pair in pairs for t in pair]
+    return desc
 
 
 def ln_grad_reduce(desc, part, n_ln, n_rep, D):
@@ -573,8 +604,12 @@ def patch_embed_bwd_ws_floats(B, C, HW, ps, D):
     return n
 
 
-def patch_embed_bwd_ws(dx, img, img_index, dWp, dbp, dcls, dpos, ws, B, C, HW, ps, D):
-    """patch_embed_bwd through per-workgroup partial sums in ``ws`` (fp32, patch_embed_bwd_ws_floats elements): no atomics, fixed order."""
+def patch_embed_bwd_ws(dx, img, img_index, dWp, dbp, dcls, dpos, ws, B, C, HW, ps, D, part_done=False):
+    """patch_embed_bwd through per-workgroup partial sums in ``ws`` (fp32, patch_embed_bwd_ws_floats elements): no atomics, fixed order.
+    part_done: dpos / dcls and the partial sums already came from the tail of gemm_tn_grouped_tail_f32 on this stream -- only the fold runs."""
+    if part_done:
+        _call("srhip_patch_embed_bwd_fold", _p(ws), _p(dWp), _p(dbp), B, C, HW, ps, D, _s())
+        return
     _call("srhip_patch_embed_bwd_ws", _p(dx), _p(img), _p(img_index), _p(dWp), _p(dbp), _p(dcls), _p(dpos), _p(ws), B, C, HW, ps, D, _s())
 
 
