@@ -204,50 +204,29 @@ class VisionTransformer(ModuleSurface):
             ops.droppath_fill(dp, self.dp_probs, self.cfg.depth, B, (self.seed << 32) + self._rng_calls, cols=cols)
         return dp
 
-    def _ctx_buffers(self, B):
+    def _ctx_buffers(self, B, precision="bf16"):
         """Activation buffers of a save=True forward.  Persistent per batch size (one live context per size), so the
-        batched-transpose / grouped-GEMM descriptor tables that point into them are built once."""
-        key = ("ctx", B)
-        if key in self._buf_cache:
-            return self._buf_cache[key]
-        cfg = self.cfg
-        D, N, H, Hd = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden
-        M = B * N
-        f32, bf16 = torch.float32, torch.bfloat16
-        mk = lambda shape, dt: [torch.empty(shape, dtype=dt, device=self.device) for _ in range(cfg.depth)]   # noqa: E731
-        ctx = FwdContext()
-        ctx.precision = "bf16"
-        ctx.xs = mk((M, D), f32) + [torch.empty(M, D, dtype=f32, device=self.device)]
-        ctx.xmid, ctx.ln1, ctx.ln2 = mk((M, D), f32), mk((M, D), bf16), mk((M, D), bf16)
-        ctx.qkv, ctx.ao, ctx.pre = mk((M, 3 * D), bf16), mk((M, D), bf16), mk((M, Hd), bf16)
-        ctx.h = mk((M, Hd), bf16)                # GELU output: the X operand of dW_fc2
-        ctx.lse = mk((B, H, N), f32)
-        ctx.st1 = [(t[0], t[1]) for t in mk((2, M), f32)]            # (mean, rstd) rows as ready views: indexing costs host time per launch
-        ctx.st2 = [(t[0], t[1]) for t in mk((2, M), f32)]
-        ctx.xhat = torch.empty(B, D, dtype=f32, device=self.device)
-        ctx.rstd = torch.empty(B, dtype=f32, device=self.device)
-        self._buf_cache[key] = ctx
-        return ctx
-
-    def _ctx_buffers_x3(self, B):
-        """Activation buffers of a save=True forward in bf16x3 precision: the same fields as _ctx_buffers, every activation fp32.  Persistent
-        per batch size and apart from the bf16 context's, so a captured step allocates nothing and the two modes never share a buffer."""
-        key = ("ctx3", B)
+        batched-transpose / grouped-GEMM descriptor tables that point into them are built once.  precision "bf16x3": the same fields, every
+        activation fp32 -- a context apart from the bf16 one of the same size, so a captured step allocates nothing and the two modes never
+        share a buffer."""
+        key = ("ctx" if precision == "bf16" else "ctx3", B)
         if key in self._buf_cache:
             return self._buf_cache[key]
         cfg = self.cfg
         D, N, H, Hd = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden
         M = B * N
         f32 = torch.float32
-        mk = lambda shape: [torch.empty(shape, dtype=f32, device=self.device) for _ in range(cfg.depth)]   # noqa: E731
+        act = torch.bfloat16 if precision == "bf16" else f32         # the GEMM operands among the activations
+        mk = lambda shape, dt: [torch.empty(shape, dtype=dt, device=self.device) for _ in range(cfg.depth)]   # noqa: E731
         ctx = FwdContext()
-        ctx.precision = "bf16x3"
-        ctx.xs = mk((M, D)) + [torch.empty(M, D, dtype=f32, device=self.device)]
-        ctx.xmid, ctx.ln1, ctx.ln2 = mk((M, D)), mk((M, D)), mk((M, D))
-        ctx.qkv, ctx.ao, ctx.pre, ctx.h = mk((M, 3 * D)), mk((M, D)), mk((M, Hd)), mk((M, Hd))
-        ctx.lse = mk((B, H, N))
-        ctx.st1 = [(t[0], t[1]) for t in mk((2, M))]
-        ctx.st2 = [(t[0], t[1]) for t in mk((2, M))]
+        ctx.precision = precision
+        ctx.xs = mk((M, D), f32) + [torch.empty(M, D, dtype=f32, device=self.device)]
+        ctx.xmid, ctx.ln1, ctx.ln2 = mk((M, D), f32), mk((M, D), act), mk((M, D), act)
+        ctx.qkv, ctx.ao, ctx.pre = mk((M, 3 * D), act), mk((M, D), act), mk((M, Hd), act)
+        ctx.h = mk((M, Hd), act)                 # GELU output: the X operand of dW_fc2
+        ctx.lse = mk((B, H, N), f32)
+        ctx.st1 = [(t[0], t[1]) for t in mk((2, M), f32)]            # (mean, rstd) rows as ready views: indexing costs host time per launch
+        ctx.st2 = [(t[0], t[1]) for t in mk((2, M), f32)]
         ctx.xhat = torch.empty(B, D, dtype=f32, device=self.device)
         ctx.rstd = torch.empty(B, dtype=f32, device=self.device)
         self._buf_cache[key] = ctx
@@ -271,12 +250,11 @@ class VisionTransformer(ModuleSurface):
         if precision == "bf16x3":
             if save:
                 assert self.grad_rows_precision == "bf16x3", "a bf16x3 forward with saved activations needs model.grad_rows_precision = 'bf16x3'"
-                return self._forward_x3_save(img, img_index, droppath, B, out)
-            return self._forward_x3(img, img_index, droppath, B, buftag, out, tree)
+            return self._forward_x3(img, img_index, droppath, B, buftag, out, tree, save)
         if precision != "bf16":
             raise ValueError("precision must be 'bf16' or 'bf16x3', got %r" % (precision,))
         cfg = self.cfg
-        D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
+        D, N, H, Hd = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden
         B = tree.n if tree is not None else (int(img_index.numel()) if img_index is not None else (B or img.shape[0]))
         M = B * N
         Mk = max(M, (kernels_as_images or 0) * N)       # the launch size the kernel choice is made for
@@ -301,18 +279,8 @@ class VisionTransformer(ModuleSurface):
         qkvx = self._buf(tag + "qkvx", (B, 3 * D), bf16) if (fused_attn and N == 257) else None
         wb = self.flat_bf16
         P = self.p
-        Kp = cfg.in_chans * cfg.patch_size ** 2
         Be, idx_e = (tree.U, tree.uimg_dev) if tree is not None else (B, img_index)       # the images the patch embedding runs on
-        if Kp <= 64:                                # CIFAR-style 2x2 / 4x4 patches: direct fp32 kernel
-            ops.patch_embed_fwd(img, idx_e, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("cls_token"),
-                                P("pos_embed"), x, Be, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
-        else:                                       # ViT-S/16 at 224: unfold (bf16) -> GEMM with the [D, 768] filter -> + bias / pos / cls
-            Np = N - 1
-            col = self._buf(tag + "col", (B * Np, Kp), bf16)
-            tok = self._buf(tag + "tok", (B * Np, D), f32)
-            ops.patch_im2col(img, idx_e, col, Be, cfg.in_chans, cfg.img_size, cfg.patch_size)
-            ops.gemm_nt(ops.EPI_F32, col, P("patch_embed.proj.weight", wb), tok, Be * Np, D, Kp, **(dict(plan_M=B * Np) if tree is not None else {}))
-            ops.patch_assemble(tok, P("patch_embed.proj.bias"), P("cls_token"), P("pos_embed"), x, Be, Np, D)
+        self._patch_embed(img, idx_e, x, Be, B, tag, "bf16", B * (N - 1) if tree is not None else None)
         scale = 64 ** -0.5
         dst0, dst1 = (droppath.stride(0), droppath.stride(1)) if droppath is not None else (0, 0)      # (a column range of the step's table: strided rows)
         ln_ready = False           # the previous block's fused launch already wrote this block's norm1 output
@@ -376,68 +344,88 @@ class VisionTransformer(ModuleSurface):
                     ops.gemm_nt(ops.EPI_GELU_BF16, ln, P(b + "mlp.fc1.weight", wb), hbuf, M, Hd, D, bias=P(b + "mlp.fc1.bias"), **gp)
                     ops.gemm_nt(ops.EPI_RESID_F32, hbuf, P(b + "mlp.fc2.weight", wb), x, M, D, Hd, bias=P(b + "mlp.fc2.bias"),
                                 row_scale=s2, rows_per_sample=N, **gp)
-        if tree is not None:
-            return self._tree_head(x, tree, out, tag, B)
-        if out is not None:
-            # out = (logits_all, feats_all, rows): the head writes image b's outputs to row rows[b] of the caller's buffers (the step's
-            # [(pass, image), .] tables) -- no index_copy_ launches behind this forward; the dense feat is only kept for a backward
-            logits_all, feats_all, rows = out
-            feat = torch.empty(B, D, dtype=f32, device=self.device) if save else None
-            logits = torch.empty(B, C, dtype=f32, device=self.device) if save else None
-            if save:
-                ctx.feat = feat
-            ops.cls_head_fwd_scatter(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits,
-                                     ctx.xhat if save else None, ctx.rstd if save else None, feats_all, logits_all, rows, B, N, D, C)
-            return logits, feat, ctx
-        feat = torch.empty(B, D, dtype=f32, device=self.device)
-        logits = torch.empty(B, C, dtype=f32, device=self.device)
-        if save:
-            ctx.feat = feat
-        ops.cls_head_fwd(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits,
-                         ctx.xhat if save else None, ctx.rstd if save else None, B, N, D, C)
-        return logits, feat, ctx
+        return self._head(x, B, out, ctx, tree, tag)
 
-    def _tree_head(self, x, tree, out, tag, n_nodes):
-        """Head of a pass-prefix tree forward: final norm + head over the last block's nodes into dense node tables, then every column's row of
-        the step's tables takes its node's outputs (the same head kernel and values as the unshared launch's scatter head)."""
+    def _patch_embed(self, img, idx, x, Be, B, tag, precision, plan_M=None):
+        """Patch embedding of the ``Be`` images ``idx`` of ``img`` into the residual stream ``x`` (workspaces: those of a launch of B images
+        under ``tag``).  plan_M (bf16): the GEMM takes the tile kernel of a launch of that many rows (a pass-prefix tree embeds fewer images
+        than the unshared launch; the x3 tile kernels are fixed: no plan to pin)."""
+        cfg = self.cfg
+        D, Np, Kp = cfg.embed_dim, cfg.num_tokens - 1, cfg.in_chans * cfg.patch_size ** 2
+        P = self.p
+        if Kp <= 64:                                # CIFAR-style 2x2 / 4x4 patches: direct fp32 kernel (either precision)
+            ops.patch_embed_fwd(img, idx, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("cls_token"),
+                                P("pos_embed"), x, Be, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
+            return
+        # ViT-S/16 at 224: unfold -> GEMM with the [D, 768] filter -> + bias / pos / cls
+        x3 = precision == "bf16x3"
+        col = self._buf(tag + "col", (B * Np, Kp), torch.float32 if x3 else torch.bfloat16)
+        tok = self._buf(tag + "tok", (B * Np, D), torch.float32)
+        if x3:                                      # fp32 unfold, bf16x3 product with the fp32 filter
+            ops.patch_im2col_f32(img, idx, col, Be, cfg.in_chans, cfg.img_size, cfg.patch_size)
+            ops.gemm_nt_x3(ops.X3_EPI_F32, col, P("patch_embed.proj.weight"), tok, Be * Np, D, Kp)
+        else:
+            ops.patch_im2col(img, idx, col, Be, cfg.in_chans, cfg.img_size, cfg.patch_size)
+            ops.gemm_nt(ops.EPI_F32, col, P("patch_embed.proj.weight", self.flat_bf16), tok, Be * Np, D, Kp, plan_M=plan_M)
+        ops.patch_assemble(tok, P("patch_embed.proj.bias"), P("cls_token"), P("pos_embed"), x, Be, Np, D)
+
+    def _head(self, x, B, out, ctx, tree, tag):
+        """Final norm + head over the class rows of the B images (or tree nodes) in ``x``; returns forward_features' triple.
+        out = (logits_all, feats_all, rows): the head writes image b's outputs to row rows[b] of the caller's buffers (the step's
+        [(pass, image), .] tables) -- no index_copy_ launches behind this forward; the dense outputs are only kept for a backward (``ctx``).
+        tree: the head runs over the last block's nodes into dense node tables, then every column's row of the step's tables takes its node's
+        outputs (the same head kernel and values as the unshared launch's scatter head)."""
         cfg = self.cfg
         D, N, C = cfg.embed_dim, cfg.num_tokens, cfg.num_classes
         P = self.p
-        logits_all, feats_all, rows = out
-        feat = self._buf(tag + "tfeat", (tree.n, D), torch.float32)
-        logits = self._buf(tag + "tlogits", (tree.n, C), torch.float32)
-        ops.cls_head_fwd(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, None, None, n_nodes, N, D, C)
-        ops.vit_fanout(logits, feat, n_nodes, tree.col_node_dev, rows, tree.n, logits_all, feats_all, C, D)
-        return None, None, None
+        f32 = torch.float32
+        feat = logits = xhat = rstd = None
+        if tree is not None:
+            feat, logits = self._buf(tag + "tfeat", (tree.n, D), f32), self._buf(tag + "tlogits", (tree.n, C), f32)
+        elif ctx is not None or out is None:
+            feat, logits = torch.empty(B, D, dtype=f32, device=self.device), torch.empty(B, C, dtype=f32, device=self.device)
+        if ctx is not None:
+            ctx.feat, xhat, rstd = feat, ctx.xhat, ctx.rstd
+        if out is not None and tree is None:
+            logits_all, feats_all, rows = out
+            ops.cls_head_fwd_scatter(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, xhat, rstd,
+                                     feats_all, logits_all, rows, B, N, D, C)
+        else:
+            ops.cls_head_fwd(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, xhat, rstd, B, N, D, C)
+        if tree is not None:
+            logits_all, feats_all, rows = out
+            ops.vit_fanout(logits, feat, B, tree.col_node_dev, rows, tree.n, logits_all, feats_all, C, D)
+            return None, None, None
+        return logits, feat, ctx
 
-    def _forward_x3(self, img, img_index, droppath, B, buftag, out, tree=None):
-        """Inference rows in split-bf16 precision (read_rows_precision = bf16x3): every product is hi.hi + hi.lo + lo.hi of the bf16 planes of
-        its fp32 operands (csrc/precise.hip), activations stay fp32, LayerNorm / softmax / GELU / residual / head in fp32 in the order of
-        vit.py.  The weights are read from the fp32 parameter block.  Own workspaces (tag "p"): the bf16 chain's buffers are not touched."""
+    def _forward_x3(self, img, img_index, droppath, B, buftag, out, tree=None, save=False):
+        """forward_features in split-bf16 precision (read_rows_precision / grad_rows_precision = bf16x3): every product is hi.hi + hi.lo +
+        lo.hi of the bf16 planes of its fp32 operands (csrc/precise.hip), activations stay fp32, LayerNorm / softmax / GELU / residual / head
+        in fp32 in the order of vit.py.  The weights are read from the fp32 parameter block.  Own workspaces (tag "p"): the bf16 chain's
+        buffers are not touched.  save: the same products and order, every activation kept fp32 in the persistent context of
+        _ctx_buffers(B, "bf16x3") (LayerNorm statistics, the fc1 pre-activation, the attention lse) for backward(ctx.precision = "bf16x3")."""
         cfg = self.cfg
-        D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
+        D, N, H, Hd = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden
         B = tree.n if tree is not None else (int(img_index.numel()) if img_index is not None else (B or img.shape[0]))
         M = B * N
         f32 = torch.float32
-        tag = "p" + buftag
-        x = self._buf(tag + "x", (M, D), f32)
-        ln = self._buf(tag + "ln", (M, D), f32)
-        ao = self._buf(tag + "ao", (M, D), f32)
-        wide = self._buf(tag + "wide", (M * max(3 * D, Hd),), f32)     # qkv [M, 3D], then the MLP hidden [M, Hd] of the same block
-        qkv, hbuf = wide[:M * 3 * D].view(M, 3 * D), wide[:M * Hd].view(M, Hd)
+        ctx = None
+        if save:
+            tag = "q"
+            ctx = self._ctx_buffers(B, "bf16x3")
+            ctx.B, ctx.img, ctx.img_index, ctx.dp = B, img, img_index, droppath
+            x = ctx.xs[0]
+        else:
+            tag = "p" + buftag
+            x = self._buf(tag + "x", (M, D), f32)
+            ln = ln2 = self._buf(tag + "ln", (M, D), f32)
+            ao = self._buf(tag + "ao", (M, D), f32)
+            wide = self._buf(tag + "wide", (M * max(3 * D, Hd),), f32)     # qkv [M, 3D], then the MLP hidden [M, Hd] of the same block
+            qkv, hbuf = wide[:M * 3 * D].view(M, 3 * D), wide[:M * Hd].view(M, Hd)
+            st1 = st2 = (None, None)
         P = self.p
-        Kp = cfg.in_chans * cfg.patch_size ** 2
-        Be, idx_e = (tree.U, tree.uimg_dev) if tree is not None else (B, img_index)       # (the x3 tile kernels are fixed: no plan to pin)
-        if Kp <= 64:                                # CIFAR-style patches: the direct kernel is fp32 already
-            ops.patch_embed_fwd(img, idx_e, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("cls_token"),
-                                P("pos_embed"), x, Be, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
-        else:                                       # ViT-S/16 at 224: fp32 unfold -> bf16x3 GEMM with the fp32 filter -> + bias / pos / cls
-            Np = N - 1
-            col = self._buf(tag + "col", (B * Np, Kp), f32)
-            tok = self._buf(tag + "tok", (B * Np, D), f32)
-            ops.patch_im2col_f32(img, idx_e, col, Be, cfg.in_chans, cfg.img_size, cfg.patch_size)
-            ops.gemm_nt_x3(ops.X3_EPI_F32, col, P("patch_embed.proj.weight"), tok, Be * Np, D, Kp)
-            ops.patch_assemble(tok, P("patch_embed.proj.bias"), P("cls_token"), P("pos_embed"), x, Be, Np, D)
+        Be, idx_e = (tree.U, tree.uimg_dev) if tree is not None else (B, img_index)
+        self._patch_embed(img, idx_e, x, Be, B, tag, "bf16x3")
         scale = 64 ** -0.5
         dst0, dst1 = (droppath.stride(0), droppath.stride(1)) if droppath is not None else (0, 0)
         for i in range(cfg.depth):
@@ -451,82 +439,32 @@ class VisionTransformer(ModuleSurface):
                 tree.launched.append(B)
             s1 = ops.RawRows(droppath, i * dst0) if droppath is not None else None
             s2 = ops.RawRows(droppath, i * dst0 + dst1) if droppath is not None else None
-            ops.layernorm_fwd_f32(x, P(b + "norm1.weight"), P(b + "norm1.bias"), cfg.eps, ln, None, None, M, D)
+            if save:
+                ln, ln2, qkv, ao, hbuf, st1, st2 = ctx.ln1[i], ctx.ln2[i], ctx.qkv[i], ctx.ao[i], ctx.h[i], ctx.st1[i], ctx.st2[i]
+            ops.layernorm_fwd_f32(x, P(b + "norm1.weight"), P(b + "norm1.bias"), cfg.eps, ln, st1[0], st1[1], M, D)
             ops.gemm_nt_x3(ops.X3_EPI_F32, ln, P(b + "attn.qkv.weight"), qkv, M, 3 * D, D, bias=P(b + "attn.qkv.bias"))
-            ops.attn_fwd_x3(qkv, ao, B, N, H, scale)
-            ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, ao, P(b + "attn.proj.weight"), x, M, D, D, bias=P(b + "attn.proj.bias"),
+            if save:
+                ops.attn_fwd_x3_lse(qkv, ao, ctx.lse[i], B, N, H, scale)
+                xm = ctx.xmid[i]
+                xm.copy_(x)                                 # the residual stream of the block input stays for the LayerNorm backward
+            else:
+                ops.attn_fwd_x3(qkv, ao, B, N, H, scale)
+                xm = x                                      # in place when nothing is saved
+            ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, ao, P(b + "attn.proj.weight"), xm, M, D, D, bias=P(b + "attn.proj.bias"),
                            row_scale=s1, rows_per_sample=N)
-            ops.layernorm_fwd_f32(x, P(b + "norm2.weight"), P(b + "norm2.bias"), cfg.eps, ln, None, None, M, D)
-            ops.gemm_nt_x3(ops.X3_EPI_GELU_F32, ln, P(b + "mlp.fc1.weight"), hbuf, M, Hd, D, bias=P(b + "mlp.fc1.bias"))
-            ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, hbuf, P(b + "mlp.fc2.weight"), x, M, D, Hd, bias=P(b + "mlp.fc2.bias"),
-                           row_scale=s2, rows_per_sample=N)
-        if tree is not None:
-            return self._tree_head(x, tree, out, tag, B)
-        if out is not None:
-            logits_all, feats_all, rows = out
-            ops.cls_head_fwd_scatter(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), None, None, None, None,
-                                     feats_all, logits_all, rows, B, N, D, C)
-            return None, None, None
-        feat = torch.empty(B, D, dtype=f32, device=self.device)
-        logits = torch.empty(B, C, dtype=f32, device=self.device)
-        ops.cls_head_fwd(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, None, None, B, N, D, C)
-        return logits, feat, None
-
-    def _forward_x3_save(self, img, img_index, droppath, B, out):
-        """_forward_x3 for rows with a backward: the same products and order, every activation kept fp32 in the persistent context of
-        _ctx_buffers_x3 (LayerNorm statistics, the fc1 pre-activation, the attention lse) for backward(ctx.precision = "bf16x3")."""
-        cfg = self.cfg
-        D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
-        B = int(img_index.numel()) if img_index is not None else (B or img.shape[0])
-        M = B * N
-        f32 = torch.float32
-        ctx = self._ctx_buffers_x3(B)
-        ctx.B, ctx.img, ctx.img_index, ctx.dp = B, img, img_index, droppath
-        x = ctx.xs[0]
-        P = self.p
-        Kp = cfg.in_chans * cfg.patch_size ** 2
-        if Kp <= 64:
-            ops.patch_embed_fwd(img, img_index, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("cls_token"),
-                                P("pos_embed"), x, B, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
-        else:
-            Np = N - 1
-            col = self._buf("qcol", (B * Np, Kp), f32)
-            tok = self._buf("qtok", (B * Np, D), f32)
-            ops.patch_im2col_f32(img, img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
-            ops.gemm_nt_x3(ops.X3_EPI_F32, col, P("patch_embed.proj.weight"), tok, B * Np, D, Kp)
-            ops.patch_assemble(tok, P("patch_embed.proj.bias"), P("cls_token"), P("pos_embed"), x, B, Np, D)
-        scale = 64 ** -0.5
-        dst0, dst1 = (droppath.stride(0), droppath.stride(1)) if droppath is not None else (0, 0)
-        for i in range(cfg.depth):
-            b = "blocks.%d." % i
-            s1 = ops.RawRows(droppath, i * dst0) if droppath is not None else None
-            s2 = ops.RawRows(droppath, i * dst0 + dst1) if droppath is not None else None
-            ops.layernorm_fwd_f32(x, P(b + "norm1.weight"), P(b + "norm1.bias"), cfg.eps, ctx.ln1[i], ctx.st1[i][0], ctx.st1[i][1], M, D)
-            ops.gemm_nt_x3(ops.X3_EPI_F32, ctx.ln1[i], P(b + "attn.qkv.weight"), ctx.qkv[i], M, 3 * D, D, bias=P(b + "attn.qkv.bias"))
-            ops.attn_fwd_x3_lse(ctx.qkv[i], ctx.ao[i], ctx.lse[i], B, N, H, scale)
-            xm = ctx.xmid[i]
-            xm.copy_(x)                                 # the residual stream of the block input stays for the LayerNorm backward
-            ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, ctx.ao[i], P(b + "attn.proj.weight"), xm, M, D, D, bias=P(b + "attn.proj.bias"),
-                           row_scale=s1, rows_per_sample=N)
-            ops.layernorm_fwd_f32(xm, P(b + "norm2.weight"), P(b + "norm2.bias"), cfg.eps, ctx.ln2[i], ctx.st2[i][0], ctx.st2[i][1], M, D)
-            ops.gemm_x3(ops.X3B_NT, ops.X3B_EPI_GELU_PRE, ctx.ln2[i], P(b + "mlp.fc1.weight"), ctx.h[i], M, Hd, D, bias=P(b + "mlp.fc1.bias"),
-                        aux_out=ctx.pre[i], ldaux=Hd)
-            xn = ctx.xs[i + 1]
-            xn.copy_(xm)
-            ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, ctx.h[i], P(b + "mlp.fc2.weight"), xn, M, D, Hd, bias=P(b + "mlp.fc2.bias"),
+            ops.layernorm_fwd_f32(xm, P(b + "norm2.weight"), P(b + "norm2.bias"), cfg.eps, ln2, st2[0], st2[1], M, D)
+            if save:
+                ops.gemm_x3(ops.X3B_NT, ops.X3B_EPI_GELU_PRE, ln2, P(b + "mlp.fc1.weight"), hbuf, M, Hd, D, bias=P(b + "mlp.fc1.bias"),
+                            aux_out=ctx.pre[i], ldaux=Hd)
+                xn = ctx.xs[i + 1]
+                xn.copy_(xm)
+            else:
+                ops.gemm_nt_x3(ops.X3_EPI_GELU_F32, ln2, P(b + "mlp.fc1.weight"), hbuf, M, Hd, D, bias=P(b + "mlp.fc1.bias"))
+                xn = xm
+            ops.gemm_nt_x3(ops.X3_EPI_RESID_F32, hbuf, P(b + "mlp.fc2.weight"), xn, M, D, Hd, bias=P(b + "mlp.fc2.bias"),
                            row_scale=s2, rows_per_sample=N)
             x = xn
-        feat = torch.empty(B, D, dtype=f32, device=self.device)
-        logits = torch.empty(B, C, dtype=f32, device=self.device)
-        ctx.feat = feat
-        if out is not None:
-            logits_all, feats_all, rows = out
-            ops.cls_head_fwd_scatter(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, ctx.xhat,
-                                     ctx.rstd, feats_all, logits_all, rows, B, N, D, C)
-        else:
-            ops.cls_head_fwd(x, P("norm.weight"), P("norm.bias"), cfg.eps, P("head.weight"), P("head.bias"), feat, logits, ctx.xhat, ctx.rstd,
-                             B, N, D, C)
-        return logits, feat, ctx
+        return self._head(x, B, out, ctx, tree, tag)
 
     def forward(self, x, only_fc=False, only_feat=False, **kw):
         """Reference-compatible entry (vit.py:285-306): returns {'logits','feat'}.  Inference-style call
@@ -543,13 +481,16 @@ class VisionTransformer(ModuleSurface):
         """Per-layer output-gradient buffers (the A operands of dW = dY^T X, kept until the ONE grouped launch after the layer
         loop) + the descriptor table of that launch (built once per batch size; ``ctx`` buffers are persistent too).
         Operands stay row-major [tokens, features]: srhip_gemm_tn_grouped_f32 gathers the MFMA fragments with LDS transpose
-        reads, and sums the bias gradients on the way (no transposes, no column-sum kernels)."""
+        reads, and sums the bias gradients on the way (no transposes, no column-sum kernels).
+        A bf16x3 context: fp32 gradient buffers and the srhip_gemm_tn_x3_grouped table of the same problems."""
         key = ("bwdplan", M, id(ctx))
         if key in self._buf_cache:
             return self._buf_cache[key]
         cfg = self.cfg
         D, Hd = cfg.embed_dim, cfg.hidden
-        mk = lambda c: torch.empty(M, c, dtype=torch.bfloat16, device=self.device)   # noqa: E731
+        x3 = ctx.precision == "bf16x3"
+        make_desc = ops.make_group_tn_x3_desc if x3 else ops.make_group_tn_desc
+        mk = lambda c: torch.empty(M, c, dtype=torch.float32 if x3 else torch.bfloat16, device=self.device)   # noqa: E731
         layers, problems = [], []
         G = lambda n: self.view(n, self.grad)   # noqa: E731
         for i in range(cfg.depth):
@@ -560,26 +501,32 @@ class VisionTransformer(ModuleSurface):
                          (t["dpre"], ctx.ln2[i], G(b + "mlp.fc1.weight"), G(b + "mlp.fc1.bias"), Hd, D, M),
                          (t["g1"], ctx.ao[i], G(b + "attn.proj.weight"), G(b + "attn.proj.bias"), D, D, M),
                          (t["dqkv"], ctx.ln1[i], G(b + "attn.qkv.weight"), G(b + "attn.qkv.bias"), 3 * D, D, M)]
-        out = dict(layers=layers, desc=ops.make_group_tn_desc(problems, self.device))
+        out = dict(layers=layers, desc=make_desc(problems, self.device))
         # LayerNorm affine gradients: LN_REP partial copies per LayerNorm (same-address atomics of ~500 workgroups serialise), folded into
         # the gradient block by ONE launch after the layer loop.  Order: norm1, norm2 of block 0, 1, ...
+        ln_names = lambda lo_l, hi_l: [(G("blocks.%d.norm%d.weight" % (i, j)), G("blocks.%d.norm%d.bias" % (i, j)))   # noqa: E731
+                                       for i in range(lo_l, hi_l) for j in (1, 2)]
         out["ln_part"] = torch.zeros(2 * cfg.depth, LN_REP, 2, D, dtype=torch.float32, device=self.device)
-        out["ln_desc"] = ops.make_ln_reduce_desc([(G("blocks.%d.norm%d.weight" % (i, j)), G("blocks.%d.norm%d.bias" % (i, j)))
-                                                  for i in range(cfg.depth) for j in (1, 2)], self.device)
-        # Data parallel: the same launches cut into DW_GROUPS layer groups (last layers first), so that the all-reduce of a group's slice of the
-        # flat gradient block can travel under the backward of the earlier layers (grad_ready_cb, see distributed.py).
-        ng = max(1, min(DW_GROUPS, cfg.depth))
-        per = -(-cfg.depth // ng)
-        groups = []
-        for hi_l in range(cfg.depth, 0, -per):
-            lo_l = max(0, hi_l - per)
+        out["ln_desc"] = ops.make_ln_reduce_desc(ln_names(0, cfg.depth), self.device)
+
+        def flat_range(lo_l, hi_l):         # the layers' parameters in the flat block
             names = [n for n, _ in self.names_shapes if n.startswith("blocks.") and lo_l <= int(n.split(".")[1]) < hi_l]
             lo = min(self.offsets[n][0] for n in names)
             hi = max(self.offsets[n][0] + int(torch.Size(self.offsets[n][1]).numel()) for n in names)
             assert sum(int(torch.Size(self.offsets[n][1]).numel()) for n in names) == hi - lo, "block parameters are contiguous in the flat block"
-            groups.append(dict(lo_layer=lo_l, hi_layer=hi_l, flat=(lo, hi), desc=ops.make_group_tn_desc(problems[4 * lo_l:4 * hi_l], self.device),
-                               ln_desc=ops.make_ln_reduce_desc([(G("blocks.%d.norm%d.weight" % (i, j)), G("blocks.%d.norm%d.bias" % (i, j)))
-                                                                for i in range(lo_l, hi_l) for j in (1, 2)], self.device)))
+            return lo, hi
+        out["flat"] = flat_range(0, cfg.depth)          # the data-parallel hand-over of a chain that launched no group: one whole-range call
+        # Data parallel: the same launches cut into DW_GROUPS layer groups (last layers first), so that the all-reduce of a group's slice of the
+        # flat gradient block can travel under the backward of the earlier layers (grad_ready_cb, see distributed.py).  (bf16 only.)
+        groups = []
+        if not x3:
+            ng = max(1, min(DW_GROUPS, cfg.depth))
+            per = -(-cfg.depth // ng)
+            for hi_l in range(cfg.depth, 0, -per):
+                lo_l = max(0, hi_l - per)
+                groups.append(dict(lo_layer=lo_l, hi_layer=hi_l, flat=flat_range(lo_l, hi_l),
+                                   desc=make_desc(problems[4 * lo_l:4 * hi_l], self.device),
+                                   ln_desc=ops.make_ln_reduce_desc(ln_names(lo_l, hi_l), self.device)))
         out["groups"] = groups
         self._buf_cache[key] = out
         return out
@@ -590,7 +537,8 @@ class VisionTransformer(ModuleSurface):
         self.backward_finish(ctx, dlogits)
 
     def _bwd_views(self, ctx, T, b0, b1):
-        """Per-layer operands of the dX chain restricted to the images [b0, b1) (built once per range: a view costs ~3 us of host time)."""
+        """Per-layer operands of the dX chain restricted to the images [b0, b1) (built once per range: a view costs ~3 us of host time).
+        The workspaces are per precision (b_* bf16 / fp32, b3_* all fp32): chains of the two precisions never share one."""
         key = ("bwdviews", id(ctx), b0, b1)
         v = self._buf_cache.get(key)
         if v is not None:
@@ -599,13 +547,14 @@ class VisionTransformer(ModuleSurface):
         D, N, H = cfg.embed_dim, cfg.num_tokens, cfg.num_heads
         B = ctx.B
         M = B * N
-        f32, bf16 = torch.float32, torch.bfloat16
+        f32 = torch.float32
+        ws, wdt = ("b3_", f32) if ctx.precision == "bf16x3" else ("b_", torch.bfloat16)
         whole = b0 == 0 and b1 == B
         r = (lambda t: t) if whole else (lambda t: t[b0 * N:b1 * N])            # rows of a [M, .] buffer
         im = (lambda t: t) if whole else (lambda t: t[b0:b1])                   # images of a [B, ..] buffer
         v = types.SimpleNamespace()
-        v.dx, v.dln, v.dao = r(self._buf("b_dx", (M, D), f32)), r(self._buf("b_dln", (M, D), bf16)), r(self._buf("b_dao", (M, D), bf16))
-        v.delta = im(self._buf("b_delta", (B, H, N), f32))
+        v.dx, v.dln, v.dao = r(self._buf(ws + "dx", (M, D), f32)), r(self._buf(ws + "dln", (M, D), wdt)), r(self._buf(ws + "dao", (M, D), wdt))
+        v.delta = im(self._buf(ws + "delta", (B, H, N), f32))
         v.xhat, v.rstd = im(ctx.xhat), im(ctx.rstd)
         v.layers = []
         for i in range(cfg.depth):
@@ -622,16 +571,21 @@ class VisionTransformer(ModuleSurface):
         different images never meet before the weight-gradient products, so disjoint ranges may run on different streams at different times
         (measured in round 5 and not used by the step: profiles/r05_early_sup_backward_ab.txt; backward() runs ONE whole-batch chain).  ``dlogits``
         is the whole [B, C] buffer; only its rows [b0, b1) are read.  LayerNorm / final-norm affine gradients are added with atomics into the
-        partial copies; everything that sums over ALL rows -- weight, bias, head and patch-embedding gradients -- is backward_finish."""
-        if ctx.precision == "bf16x3":
-            return self._backward_rows_x3(ctx, dlogits, b0, b1)
+        partial copies; everything that sums over ALL rows -- weight, bias, head and patch-embedding gradients -- is backward_finish.
+        A bf16x3 context: the same chain with fp32 gradients, every input-gradient product dY . W a split-bf16 NN product on the fp32
+        parameter block (no transposed copies), the attention backward and the LayerNorm backward on fp32 operands."""
         cfg = self.cfg
         D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
         nb = b1 - b0
         M = nb * N
         P = self.p
         G = lambda n: self.p(n, self.grad)   # noqa: E731
-        self.ensure_transposed()
+        x3 = ctx.precision == "bf16x3"
+        if x3:
+            ln_bwd, attn_bwd, NN, X3F = ops.layernorm_bwd_part_f32, ops.attn_bwd_x3, ops.X3B_NN, ops.X3B_EPI_F32
+        else:
+            ln_bwd, attn_bwd, wT = ops.layernorm_bwd_part, ops.attn_bwd, self.wT
+            self.ensure_transposed()
         T = self._bwd_plan(ctx.B * N, ctx)
         v = self._bwd_views(ctx, T, b0, b1)
         dl = dlogits if (b0 == 0 and b1 == ctx.B) else dlogits[b0:b1]
@@ -641,28 +595,38 @@ class VisionTransformer(ModuleSurface):
         scale = 64 ** -0.5
         dp = ctx.dp
         lnp = T["ln_part"]
-        cb = self.grad_ready_cb if (b0 == 0 and b1 == ctx.B) else None          # data parallel overlap: whole-batch chains only
+        cb = self.grad_ready_cb if (b0 == 0 and b1 == ctx.B and not x3) else None   # data parallel overlap: whole-batch bf16 chains only
         self._groups_launched = cb is not None         # backward_finish: the layer groups' weight / LayerNorm launches already ran inside this chain
         gdone = {g["lo_layer"]: g for g in T["groups"]} if cb is not None else {}
         # dp[i, j, b0:] as a raw pointer (the DropPath factors of this range's images)
         dpr = (lambda i_, j_: ops.RawRows(dp, i_ * dp.stride(0) + j_ * dp.stride(1) + b0)) if dp is not None else (lambda i_, j_: None)
         L = v.layers
-        ops.cast_scale_rows(v.dx, dpr(cfg.depth - 1, 1), N, L[cfg.depth - 1].g2, M, D)
+        (ops.scale_rows_f32 if x3 else ops.cast_scale_rows)(v.dx, dpr(cfg.depth - 1, 1), N, L[cfg.depth - 1].g2, M, D)
         for i in reversed(range(cfg.depth)):
             b = "blocks.%d." % i
             Li = L[i]
             s1 = dpr(i, 0)
-            # ---- MLP branch: x_out = x_mid + s2 * fc2(gelu(fc1(ln2(x_mid))));  g2 = bf16(s2 * dx) came from the previous LayerNorm backward
-            ops.gemm_nt(ops.EPI_DGELU_BF16, Li.g2, self.wT[b + "mlp.fc2.weight"], Li.dpre, M, Hd, D, aux_in=Li.pre, ldaux=Hd)
-            ops.gemm_nt(ops.EPI_BF16, Li.dpre, self.wT[b + "mlp.fc1.weight"], v.dln, M, D, Hd)
-            ops.layernorm_bwd_part(v.dln, Li.xmid, Li.st2[0], Li.st2[1], P(b + "norm2.weight"), v.dx, lnp[2 * i + 1], LN_REP,
-                                   Li.g1, s1, N, M, D)
-            # ---- attention branch: x_mid = x_in + s1 * proj(attn(qkv(ln1(x_in))))
-            ops.gemm_nt(ops.EPI_BF16, Li.g1, self.wT[b + "attn.proj.weight"], v.dao, M, D, D)
-            ops.attn_bwd(Li.qkv, Li.ao, v.dao, Li.lse, Li.dqkv, v.delta, nb, N, H, scale)
-            ops.gemm_nt(ops.EPI_BF16, Li.dqkv, self.wT[b + "attn.qkv.weight"], v.dln, M, D, 3 * D)
-            ops.layernorm_bwd_part(v.dln, Li.xs, Li.st1[0], Li.st1[1], P(b + "norm1.weight"), v.dx, lnp[2 * i], LN_REP,
-                                   L[i - 1].g2 if i > 0 else None, dpr(i - 1, 1) if i > 0 else None, N, M, D)
+            # ---- MLP branch: x_out = x_mid + s2 * fc2(gelu(fc1(ln2(x_mid))));  g2 = s2 * dx came from the previous LayerNorm backward;
+            # dpre = (g2 . W_fc2) * gelu'(pre); dln2 = dpre . W_fc1
+            if x3:
+                ops.gemm_x3(NN, ops.X3B_EPI_DGELU, Li.g2, P(b + "mlp.fc2.weight"), Li.dpre, M, Hd, D, aux=Li.pre, ldaux=Hd)
+                ops.gemm_x3(NN, X3F, Li.dpre, P(b + "mlp.fc1.weight"), v.dln, M, D, Hd)
+            else:
+                ops.gemm_nt(ops.EPI_DGELU_BF16, Li.g2, wT[b + "mlp.fc2.weight"], Li.dpre, M, Hd, D, aux_in=Li.pre, ldaux=Hd)
+                ops.gemm_nt(ops.EPI_BF16, Li.dpre, wT[b + "mlp.fc1.weight"], v.dln, M, D, Hd)
+            ln_bwd(v.dln, Li.xmid, Li.st2[0], Li.st2[1], P(b + "norm2.weight"), v.dx, lnp[2 * i + 1], LN_REP, Li.g1, s1, N, M, D)
+            # ---- attention branch: x_mid = x_in + s1 * proj(attn(qkv(ln1(x_in))));  g1 = s1 * dx; dao = g1 . W_proj; dqkv; dln1 = dqkv . W_qkv
+            if x3:
+                ops.gemm_x3(NN, X3F, Li.g1, P(b + "attn.proj.weight"), v.dao, M, D, D)
+            else:
+                ops.gemm_nt(ops.EPI_BF16, Li.g1, wT[b + "attn.proj.weight"], v.dao, M, D, D)
+            attn_bwd(Li.qkv, Li.ao, v.dao, Li.lse, Li.dqkv, v.delta, nb, N, H, scale)
+            if x3:
+                ops.gemm_x3(NN, X3F, Li.dqkv, P(b + "attn.qkv.weight"), v.dln, M, D, 3 * D)
+            else:
+                ops.gemm_nt(ops.EPI_BF16, Li.dqkv, wT[b + "attn.qkv.weight"], v.dln, M, D, 3 * D)
+            ln_bwd(v.dln, Li.xs, Li.st1[0], Li.st1[1], P(b + "norm1.weight"), v.dx, lnp[2 * i], LN_REP,
+                   L[i - 1].g2 if i > 0 else None, dpr(i - 1, 1) if i > 0 else None, N, M, D)
             g = gdone.get(i)
             if g is not None:               # layers [i, g.hi_layer) are finished: their weight / bias / LayerNorm gradients, then the hand-over
                 desc, npb, ntiles, flops, nbytes = g["desc"]
@@ -673,26 +637,26 @@ class VisionTransformer(ModuleSurface):
     def backward_finish(self, ctx, dlogits):
         """Everything of the backward that sums over ALL rows, after the chain(s) of backward_rows have covered every image: head weight / bias
         gradients, the LayerNorm partial copies folded into the gradient block, all 4 * depth weight (and bias) gradients in ONE grouped
-        launch (dW += dY^T X, db += colsum dY), the patch embedding."""
-        if ctx.precision == "bf16x3":
-            return self._backward_finish_x3(ctx, dlogits)
+        launch (dW += dY^T X, db += colsum dY; srhip_gemm_tn_x3_grouped for a bf16x3 context), the data-parallel hand-over of the blocks'
+        range when the chain did not hand it over in groups, the patch embedding."""
         cfg = self.cfg
         D, N, C = cfg.embed_dim, cfg.num_tokens, cfg.num_classes
         B = ctx.B
         M = B * N
-        f32, bf16 = torch.float32, torch.bfloat16
+        f32 = torch.float32
         G = lambda n: self.p(n, self.grad)   # noqa: E731
+        x3 = ctx.precision == "bf16x3"
         T = self._bwd_plan(M, ctx)
-        dx = self._buf("b_dx", (M, D), f32)
-        Kp = cfg.in_chans * cfg.patch_size ** 2
-        small_pe = Kp <= 64                                 # the two-stage patch-embedding kernels (one thread per feature, the patch in LDS)
+        dx = self._buf("b3_dx" if x3 else "b_dx", (M, D), f32)
+        small_pe = cfg.in_chans * cfg.patch_size ** 2 <= 64    # the two-stage patch-embedding kernels (one thread per feature, the patch in LDS)
         ws = self._buf("b_pe_ws", (ops.patch_embed_bwd_ws_floats(B, cfg.in_chans, cfg.img_size, cfg.patch_size, D),), f32) if small_pe else None
-        groups_launched = getattr(self, "_groups_launched", False)    # (a partial-range chain never launches them, callback or not)
+        # (a partial-range chain never launches the groups, callback or not; nor does a bf16x3 chain)
+        groups_launched = not x3 and getattr(self, "_groups_launched", False)
         # One launch for the blocks' weight gradients AND the small sums over all rows (head weight, LayerNorm copies, dpos / dcls, stage 1 of the
         # patch-embedding gradient): they ran as latency-bound launches around the product, on the step's own stream with nothing beside them;
         # as extra workgroups they fill the slots the product's last round of tiles leaves empty.  (Not under the per-launch profiler, which times
-        # the product alone -- DESIGN.md section 7 -- nor for a table with a slab phase.)
-        merged = not groups_launched and ops._PROFILE is None and getattr(T["desc"][0], "reduce", None) is None
+        # the product alone -- DESIGN.md section 7 -- nor for a table with a slab phase, nor for the x3 product.)
+        merged = not x3 and not groups_launched and ops._PROFILE is None and getattr(T["desc"][0], "reduce", None) is None
         desc, npb, ntiles, flops, nbytes = T["desc"]
         if merged:
             pe = (dx, ctx.img, ctx.img_index, G("pos_embed"), G("cls_token"), ws, B, cfg.in_chans, cfg.img_size, cfg.patch_size) if small_pe else None
@@ -702,159 +666,45 @@ class VisionTransformer(ModuleSurface):
             ops.cls_head_bwd(dlogits, None, None, ctx.feat, None, None, None, G("head.weight"), G("head.bias"), None, None, B, N, D, C)
             if not groups_launched:
                 ops.ln_grad_reduce(T["ln_desc"], T["ln_part"], 2 * cfg.depth, LN_REP, D)
-                ops.gemm_tn_grouped_f32(desc, npb, ntiles, alpha=1.0, beta=1.0, flops=flops, nbytes=nbytes)
+                if x3:
+                    ops.gemm_tn_x3_grouped(desc, npb, ntiles, flops=flops, nbytes=nbytes)
+                else:
+                    ops.gemm_tn_grouped_f32(desc, npb, ntiles, alpha=1.0, beta=1.0, flops=flops, nbytes=nbytes)
         if not groups_launched and self.grad_ready_cb is not None:
-            lo = min(g["flat"][0] for g in T["groups"]); hi = max(g["flat"][1] for g in T["groups"])
-            self.grad_ready_cb(lo, hi)                  # the blocks' range in one piece (the chain did not hand it over in groups)
+            self.grad_ready_cb(*T["flat"])              # the blocks' range in one piece (the chain did not hand it over in groups)
         self._groups_launched = False
-        if small_pe:
-            part_done = merged                          # dpos / dcls and stage 1 rode in the merged launch: only the fold is left
+        # dpos / dcls and stage 1 rode in the merged launch: only the fold is left
+        self._patch_embed_bwd(ctx, dx, ws, x3, part_done=merged)
+
+    def _patch_embed_bwd(self, ctx, dx, ws, x3, part_done):
+        """Patch-embedding gradients from the residual stream's gradient ``dx``: the workspace kernels (``ws``; part_done: see
+        ops.patch_embed_bwd_ws), else dWp += dx_tok^T col, dbp += colsum dx_tok as a one-problem TN grouped GEMM (operands and table built
+        once per batch size and precision) behind the dpos / dcls launch."""
+        cfg = self.cfg
+        D, Np, B = cfg.embed_dim, cfg.num_tokens - 1, ctx.B
+        G = lambda n: self.p(n, self.grad)   # noqa: E731
+        if ws is not None:
             ops.patch_embed_bwd_ws(dx, ctx.img, ctx.img_index, G("patch_embed.proj.weight"), G("patch_embed.proj.bias"), G("cls_token"),
                                    G("pos_embed"), ws, B, cfg.in_chans, cfg.img_size, cfg.patch_size, D, part_done)
-        else:                                       # dWp += dx_tok^T col, dbp += colsum dx_tok (TN grouped GEMM, one problem); dpos, dcls
-            Np = N - 1
-            key = ("pebwd", B)
-            if key not in self._buf_cache:
-                col = torch.empty(B * Np, Kp, dtype=bf16, device=self.device)
-                dxt = torch.empty(B * Np, D, dtype=bf16, device=self.device)
-                gw = self.view("patch_embed.proj.weight", self.grad).view(D, Kp)
-                desc = ops.make_group_tn_desc([(dxt, col, gw, self.view("patch_embed.proj.bias", self.grad), D, Kp, B * Np)], self.device)
-                self._buf_cache[key] = (col, dxt, desc)
-            col, dxt, desc = self._buf_cache[key]
-            ops.patch_im2col(ctx.img, ctx.img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
-            ops.patch_grad_operands(dx, dxt, G("pos_embed"), G("cls_token"), B, Np, D)
-            ops.gemm_tn_grouped_f32(desc[0], desc[1], desc[2], alpha=1.0, beta=1.0, flops=desc[3], nbytes=desc[4])
-
-    # ---- split-bf16 backward (grad_rows_precision = bf16x3) ------------------------------------------------------------------------------
-    def _bwd_plan_x3(self, M, ctx):
-        """_bwd_plan for a bf16x3 context: fp32 output-gradient buffers per layer, the srhip_gemm_tn_x3_grouped table of all 4 * depth weight
-        (and bias) gradients, the LayerNorm partial copies.  The data-parallel hand-over is one whole-range call after that launch."""
-        key = ("bwdplan3", M, id(ctx))
-        if key in self._buf_cache:
-            return self._buf_cache[key]
-        cfg = self.cfg
-        D, Hd = cfg.embed_dim, cfg.hidden
-        mk = lambda c: torch.empty(M, c, dtype=torch.float32, device=self.device)   # noqa: E731
-        G = lambda n: self.view(n, self.grad)   # noqa: E731
-        layers, problems = [], []
-        for i in range(cfg.depth):
-            b = "blocks.%d." % i
-            t = dict(g2=mk(D), dpre=mk(Hd), g1=mk(D), dqkv=mk(3 * D))
-            layers.append(t)
-            problems += [(t["g2"], ctx.h[i], G(b + "mlp.fc2.weight"), G(b + "mlp.fc2.bias"), D, Hd, M),
-                         (t["dpre"], ctx.ln2[i], G(b + "mlp.fc1.weight"), G(b + "mlp.fc1.bias"), Hd, D, M),
-                         (t["g1"], ctx.ao[i], G(b + "attn.proj.weight"), G(b + "attn.proj.bias"), D, D, M),
-                         (t["dqkv"], ctx.ln1[i], G(b + "attn.qkv.weight"), G(b + "attn.qkv.bias"), 3 * D, D, M)]
-        out = dict(layers=layers, desc=ops.make_group_tn_x3_desc(problems, self.device))
-        out["ln_part"] = torch.zeros(2 * cfg.depth, LN_REP, 2, D, dtype=torch.float32, device=self.device)
-        out["ln_desc"] = ops.make_ln_reduce_desc([(G("blocks.%d.norm%d.weight" % (i, j)), G("blocks.%d.norm%d.bias" % (i, j)))
-                                                  for i in range(cfg.depth) for j in (1, 2)], self.device)
-        names = [n for n, _ in self.names_shapes if n.startswith("blocks.")]
-        out["flat"] = (min(self.offsets[n][0] for n in names), max(self.offsets[n][0] + int(torch.Size(self.offsets[n][1]).numel()) for n in names))
-        self._buf_cache[key] = out
-        return out
-
-    def _bwd_views_x3(self, ctx, T, b0, b1):
-        """_bwd_views for a bf16x3 context (fp32 workspaces of their own)."""
-        key = ("bwdviews3", id(ctx), b0, b1)
-        v = self._buf_cache.get(key)
-        if v is not None:
-            return v
-        cfg = self.cfg
-        D, N, H = cfg.embed_dim, cfg.num_tokens, cfg.num_heads
-        B = ctx.B
-        M = B * N
-        f32 = torch.float32
-        r = lambda t: t[b0 * N:b1 * N]          # noqa: E731
-        im = lambda t: t[b0:b1]                 # noqa: E731
-        v = types.SimpleNamespace()
-        v.dx, v.dln, v.dao = r(self._buf("b3_dx", (M, D), f32)), r(self._buf("b3_dln", (M, D), f32)), r(self._buf("b3_dao", (M, D), f32))
-        v.delta = im(self._buf("b3_delta", (B, H, N), f32))
-        v.xhat, v.rstd = im(ctx.xhat), im(ctx.rstd)
-        v.layers = []
-        for i in range(cfg.depth):
-            Ti = T["layers"][i]
-            v.layers.append(types.SimpleNamespace(
-                g2=r(Ti["g2"]), dpre=r(Ti["dpre"]), g1=r(Ti["g1"]), dqkv=r(Ti["dqkv"]), pre=r(ctx.pre[i]), xmid=r(ctx.xmid[i]), xs=r(ctx.xs[i]),
-                st1=(r(ctx.st1[i][0]), r(ctx.st1[i][1])), st2=(r(ctx.st2[i][0]), r(ctx.st2[i][1])), qkv=r(ctx.qkv[i]), ao=r(ctx.ao[i]),
-                lse=im(ctx.lse[i])))
-        self._buf_cache[key] = v
-        return v
-
-    def _backward_rows_x3(self, ctx, dlogits, b0, b1):
-        """backward_rows of a bf16x3 context: the same chain with fp32 gradients, every input-gradient product dY . W a split-bf16 NN product
-        on the fp32 parameter block (no transposed copies), the attention backward and the LayerNorm backward on fp32 operands."""
-        cfg = self.cfg
-        D, N, H, Hd, C = cfg.embed_dim, cfg.num_tokens, cfg.num_heads, cfg.hidden, cfg.num_classes
-        nb = b1 - b0
-        M = nb * N
-        P = self.p
-        G = lambda n: self.p(n, self.grad)   # noqa: E731
-        T = self._bwd_plan_x3(ctx.B * N, ctx)
-        v = self._bwd_views_x3(ctx, T, b0, b1)
-        dl = dlogits if (b0 == 0 and b1 == ctx.B) else dlogits[b0:b1]
-        self._groups_launched = False
-        v.dx.zero_()
-        ops.cls_head_bwd(dl, P("head.weight"), P("norm.weight"), None, v.xhat, v.rstd, v.dx, None, None, G("norm.weight"), G("norm.bias"),
-                         nb, N, D, C)
-        scale = 64 ** -0.5
-        dp = ctx.dp
-        lnp = T["ln_part"]
-        dpr = (lambda i_, j_: ops.RawRows(dp, i_ * dp.stride(0) + j_ * dp.stride(1) + b0)) if dp is not None else (lambda i_, j_: None)
-        L = v.layers
-        ops.scale_rows_f32(v.dx, dpr(cfg.depth - 1, 1), N, L[cfg.depth - 1].g2, M, D)
-        NN = ops.X3B_NN
-        for i in reversed(range(cfg.depth)):
-            b = "blocks.%d." % i
-            Li = L[i]
-            # MLP branch: g2 = s2 * dx; dpre = (g2 . W_fc2) * gelu'(pre); dln2 = dpre . W_fc1
-            ops.gemm_x3(NN, ops.X3B_EPI_DGELU, Li.g2, P(b + "mlp.fc2.weight"), Li.dpre, M, Hd, D, aux=Li.pre, ldaux=Hd)
-            ops.gemm_x3(NN, ops.X3B_EPI_F32, Li.dpre, P(b + "mlp.fc1.weight"), v.dln, M, D, Hd)
-            ops.layernorm_bwd_part_f32(v.dln, Li.xmid, Li.st2[0], Li.st2[1], P(b + "norm2.weight"), v.dx, lnp[2 * i + 1], LN_REP,
-                                       Li.g1, dpr(i, 0), N, M, D)
-            # attention branch: g1 = s1 * dx; dao = g1 . W_proj; dqkv; dln1 = dqkv . W_qkv
-            ops.gemm_x3(NN, ops.X3B_EPI_F32, Li.g1, P(b + "attn.proj.weight"), v.dao, M, D, D)
-            ops.attn_bwd_x3(Li.qkv, Li.ao, v.dao, Li.lse, Li.dqkv, v.delta, nb, N, H, scale)
-            ops.gemm_x3(NN, ops.X3B_EPI_F32, Li.dqkv, P(b + "attn.qkv.weight"), v.dln, M, D, 3 * D)
-            ops.layernorm_bwd_part_f32(v.dln, Li.xs, Li.st1[0], Li.st1[1], P(b + "norm1.weight"), v.dx, lnp[2 * i], LN_REP,
-                                       L[i - 1].g2 if i > 0 else None, dpr(i - 1, 1) if i > 0 else None, N, M, D)
-
-    def _backward_finish_x3(self, ctx, dlogits):
-        """backward_finish of a bf16x3 context: head, LayerNorm fold, ONE srhip_gemm_tn_x3_grouped launch for all 4 * depth weight and bias
-        gradients, the data-parallel hand-over of the blocks' range in one piece, the patch embedding (fp32 kernel or a one-problem x3 table)."""
-        cfg = self.cfg
-        D, N, C = cfg.embed_dim, cfg.num_tokens, cfg.num_classes
-        B = ctx.B
-        M = B * N
-        f32 = torch.float32
-        G = lambda n: self.p(n, self.grad)   # noqa: E731
-        T = self._bwd_plan_x3(M, ctx)
-        dx = self._buf("b3_dx", (M, D), f32)
-        ops.cls_head_bwd(dlogits, None, None, ctx.feat, None, None, None, G("head.weight"), G("head.bias"), None, None, B, N, D, C)
-        ops.ln_grad_reduce(T["ln_desc"], T["ln_part"], 2 * cfg.depth, LN_REP, D)
-        desc, npb, ntiles, flops, nbytes = T["desc"]
-        ops.gemm_tn_x3_grouped(desc, npb, ntiles, flops=flops, nbytes=nbytes)
-        if self.grad_ready_cb is not None:
-            self.grad_ready_cb(*T["flat"])
-        self._groups_launched = False
-        Kp = cfg.in_chans * cfg.patch_size ** 2
-        if Kp <= 64:
-            ws = self._buf("b_pe_ws", (ops.patch_embed_bwd_ws_floats(B, cfg.in_chans, cfg.img_size, cfg.patch_size, D),), f32)
-            ops.patch_embed_bwd_ws(dx, ctx.img, ctx.img_index, G("patch_embed.proj.weight"), G("patch_embed.proj.bias"), G("cls_token"),
-                                   G("pos_embed"), ws, B, cfg.in_chans, cfg.img_size, cfg.patch_size, D)
-        else:                                       # dWp += dx_tok^T col, dbp += colsum dx_tok (one-problem x3 table); dpos, dcls
-            Np = N - 1
-            key = ("pebwd3", B)
-            if key not in self._buf_cache:
-                col = torch.empty(B * Np, Kp, dtype=f32, device=self.device)
-                dxt = torch.empty(B * Np, D, dtype=f32, device=self.device)
-                gw = self.view("patch_embed.proj.weight", self.grad).view(D, Kp)
-                desc = ops.make_group_tn_x3_desc([(dxt, col, gw, self.view("patch_embed.proj.bias", self.grad), D, Kp, B * Np)], self.device)
-                self._buf_cache[key] = (col, dxt, desc)
-            col, dxt, desc = self._buf_cache[key]
+            return
+        key = ("pebwd3" if x3 else "pebwd", B)
+        if key not in self._buf_cache:
+            Kp = cfg.in_chans * cfg.patch_size ** 2
+            dt = torch.float32 if x3 else torch.bfloat16
+            col = torch.empty(B * Np, Kp, dtype=dt, device=self.device)
+            dxt = torch.empty(B * Np, D, dtype=dt, device=self.device)
+            gw = self.view("patch_embed.proj.weight", self.grad).view(D, Kp)
+            problem = [(dxt, col, gw, self.view("patch_embed.proj.bias", self.grad), D, Kp, B * Np)]
+            self._buf_cache[key] = (col, dxt, (ops.make_group_tn_x3_desc if x3 else ops.make_group_tn_desc)(problem, self.device))
+        col, dxt, desc = self._buf_cache[key]
+        if x3:
             ops.patch_im2col_f32(ctx.img, ctx.img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
             ops.patch_grad_operands_f32(dx, dxt, G("pos_embed"), G("cls_token"), B, Np, D)
             ops.gemm_tn_x3_grouped(desc[0], desc[1], desc[2], flops=desc[3], nbytes=desc[4])
+        else:
+            ops.patch_im2col(ctx.img, ctx.img_index, col, B, cfg.in_chans, cfg.img_size, cfg.patch_size)
+            ops.patch_grad_operands(dx, dxt, G("pos_embed"), G("cls_token"), B, Np, D)
+            ops.gemm_tn_grouped_f32(desc[0], desc[1], desc[2], alpha=1.0, beta=1.0, flops=desc[3], nbytes=desc[4])
 
 
 # ---- builders with the reference's names (vit.py:323-408); pretrained=True loads pretrained_path as the reference's load_checkpoint does ----

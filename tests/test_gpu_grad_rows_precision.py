@@ -217,6 +217,13 @@ def test_vit_backward_x3_matches_fp32_autograd(tag):
     # the bf16 context of the same model is untouched by the mode (and still is the default)
     _, _, c0 = model.forward_features(x.to(DEV), None, dp.to(DEV), save=True)
     assert c0.precision == "bf16" and c0 is not ctx
+    model.zero_grad()
+    model.backward(c0, dl)
+    assert torch.isfinite(model.grad).all() and float(model.grad.abs().max()) > 0
+    # ... and the bf16 forward and backward in between left the bf16x3 context and its backward plan as they were
+    model.zero_grad()
+    model.backward(ctx, dl)
+    assert rel(model.grad, g1) < 1e-6
 
 
 # ---- steps ---------------------------------------------------------------------------------------------------------------------------------
