@@ -5,10 +5,12 @@ resizes them once on the device (Pillow's bilinear, csrc/resize.hip), builds the
 views (data/device_loader.py), and ``alg.train()`` / ``alg.evaluate()`` run with no hand-written batch generator.
 
     python examples/train_device_loader.py --steps 100
+    python examples/train_device_loader.py --steps 100 --run-hooks     # the reference's evaluation / checkpoint / logging hooks drive the run
 """
 import argparse
 import os
 import sys
+import tempfile
 
 import numpy as np
 
@@ -44,6 +46,8 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--stored-size", type=int, default=64)
+    ap.add_argument("--run-hooks", action="store_true",
+                    help="run_hooks + device_eval: evaluate and checkpoint every 20 steps (into a temporary save_dir), log every 10")
     a = ap.parse_args()
     C, H0 = a.classes, a.stored_size
     x_lb, y_lb = synth_dataset(40 * C // 10, C, 1, H0)             # "40 labels"-style split
@@ -59,10 +63,18 @@ def main():
         device_data=True,
         dataset_dict={"train_lb": {"data": x_lb, "targets": y_lb}, "train_ulb": {"data": x_ulb, "targets": None},
                       "eval": {"data": x_te, "targets": y_te}})
-    alg = get_algorithm(args, vit.vit_small_patch2_32)
-    alg.register_hook(PrintHook(), "PrintHook", "LOWEST")
-    alg.train()
-    ev = alg.evaluate("eval")
+    if a.run_hooks:
+        with tempfile.TemporaryDirectory() as save_dir:
+            vars(args).update(run_hooks=True, device_eval=True, num_eval_iter=20, num_log_iter=10, save_dir=save_dir, save_name="example")
+            alg = get_algorithm(args, vit.vit_small_patch2_32)
+            alg.train()
+            print("results:", alg.results_dict, " files:", sorted(os.listdir(os.path.join(save_dir, "example"))))
+            ev = alg.evaluate("eval")
+    else:
+        alg = get_algorithm(args, vit.vit_small_patch2_32)
+        alg.register_hook(PrintHook(), "PrintHook", "LOWEST")
+        alg.train()
+        ev = alg.evaluate("eval")
     print("eval:", {k: round(float(v), 4) for k, v in ev.items()})
     return ev
 

@@ -466,6 +466,21 @@ int srhip_consistency_l1(const float* logits, long long ld, const float* targets
                          float grad_scale, int reduction, float* loss_rows, float* loss, float* dlogits, long long ldd, int B, int C,
                          void* stream);
 
+/* Evaluation tail (semilearn/core/algorithmbase.py:377-457) of one batch in ONE launch, accumulated on the device (eval.hip).  logits fp32
+ * [B, C] with row stride ld (elements, >= C), y int64 [B].  Per row b, in fp32 with the row maximum subtracted first:
+ *   loss_b = logsumexp(z_b) - z_b[y_b]              pred_b = the first maximal column, a NaN counting as maximal (numpy / torch argmax)
+ * The caller owns and zeroes the accumulators:
+ *   confusion int32 [C + 1, C]: += 1 at [y_b, pred_b]; rows with y_b == -1 (ignore_index, :407) count in row C and stay out of the loss.
+ *   state (8-byte aligned) = { double loss_sum, nll_sum; long long rows, kept; }:
+ *     loss_sum += (sum of loss_b over the kept rows, y_b >= 0) / max(kept_in_batch, 1) * B   -- `loss.item() * num_batch` (:413), 0 for a batch
+ *     without kept rows; nll_sum += the same sum undivided; rows += rows counted in confusion; kept += kept_in_batch.
+ *   pred_out (optional, NULL = none) int64: pred_out[row_offset + b] = pred_b, for every row.
+ * A label < -1 or >= C (F.cross_entropy raises) sets bit 4 of the word srhip_label_error reads and the row reaches no accumulator.
+ * One workgroup, one wave per row; the batch sum is added in a fixed order in fp64 by one thread and launches of one stream are ordered:
+ * run-to-run bit-identical, no float atomics (the confusion counts are integer atomics).  1 <= B <= 65535, C >= 1. */
+int srhip_eval_accumulate(const float* logits, long long ld, const long long* y, int* confusion, void* state, long long* pred_out,
+                          long long row_offset, int B, int C, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Rewarder / Generator (K10, K14, K15).  params: flat fp32 block in named_parameters() order.
  * Rewarder.forward (semilearn/algorithms/semireward/semireward.py:52-72) for G independent groups of B rows
@@ -503,7 +518,8 @@ int srhip_sr_target(const long long* gen, const long long* ref, float* target, i
  * pseudo) label is outside [0, label_dim) (semireward.py:57, srflexmatch.py:180-181); the kernels stay memory safe (row 0 is read, the
  * gradient scatter is skipped), set a bit in a device word and the host raises when it reads it here (SYNCHRONISES the stream):
  * bit 0 embedding lookup, bit 1 embedding-gradient scatter, bit 2 generator output NaN / not representable as int64, bit 3 a label outside
- * [0, num_classes) in srhip_sr_target (F.one_hot; num_classes <= 0 disables that check). */
+ * [0, num_classes) in srhip_sr_target (F.one_hot; num_classes <= 0 disables that check), bit 4 an evaluation label outside [-1, C) in
+ * srhip_eval_accumulate. */
 int srhip_label_error(int* bits_out, int reset, void* stream);
 /* torch.optim.Adam step on a flat block (srflexmatch.py:54, :192-193). */
 /* "_dyn" entry points: the scalars that change from step to step -- the scheduler's lr factor and Adam's bias corrections (param_update.py:33-40,

@@ -21,7 +21,8 @@ from .. import ops
 from ..distributed import DataParallel
 from ..optim import FusedAdamW, FusedSGD
 from .criterions import CELoss, ConsistencyLoss
-from .hooks import DistSamplerSeedHook, EMAHook, Hook, ParamUpdateHook, TimerHook, get_priority
+from .hooks import (CheckpointHook, DistSamplerSeedHook, EMAHook, EvaluationHook, Hook, LoggingHook, ParamUpdateHook, TimerHook,
+                    get_priority)
 from .utils import reference_data_functions
 
 
@@ -90,6 +91,7 @@ class AlgorithmBase:
         self.rank = g("rank", 0)
         self.distributed = g("distributed", False)
         self.world_size = g("world_size", 1)
+        self.ngpus_per_node = max(torch.cuda.device_count(), 1)      # algorithmbase.py:93: the first rank of a node writes checkpoints and logs
         # (without a GPU only the host-side wiring of this class can be exercised -- tests/test_cpu_driver_contract.py; every op raises)
         self.device = torch.device("cuda", self.gpu if isinstance(self.gpu, int) else torch.cuda.current_device()) \
             if torch.cuda.is_available() else torch.device("cpu")
@@ -101,6 +103,8 @@ class AlgorithmBase:
         self.net_builder = net_builder
         self.ema = None
         self.device_data = bool(g("device_data", False))     # dataset arrays resident in HBM, loaders of data/device_loader.py
+        self.device_eval = bool(g("device_eval", False))     # evaluate() accumulates loss and confusion matrix on the device (csrc/eval.hip)
+        self.run_hooks = bool(g("run_hooks", False))         # the reference's EvaluationHook / CheckpointHook / LoggingHook join the hook list
         self.dataset_dict = self.set_dataset()
         self.loader_dict = self.set_data_loader()
         self.model = self.set_model()
@@ -212,7 +216,12 @@ class AlgorithmBase:
     def set_hooks(self):
         self.register_hook(ParamUpdateHook(), None, "HIGHEST")
         self.register_hook(EMAHook(), None, "HIGH")
+        if self.run_hooks:                                        # algorithmbase.py:272-273: evaluate, then save (the best model needs the result)
+            self.register_hook(EvaluationHook(), None, "HIGH")
+            self.register_hook(CheckpointHook(), None, "HIGH")
         self.register_hook(TimerHook(), None, "LOWEST")           # algorithmbase.py:564: train/prefetch_time, train/run_time, lr
+        if self.run_hooks:
+            self.register_hook(LoggingHook(), None, "LOWEST")     # after TimerHook: the line holds lr and the timings
 
     # ---- batch / dict helpers (algorithmbase.py:282-333) -------------------------------------------
     def process_batch(self, input_args=None, **kwargs):
@@ -302,12 +311,39 @@ class AlgorithmBase:
         return {"top-1-acc": float(tp.sum() / max(y_true.size, 1)), "balanced_acc": float(rec[sup > 0].mean()),
                 "precision": float(prec.mean()), "recall": float(rec.mean()), "F1": float(f1.mean())}
 
+    @staticmethod
+    def _present_confusion(cm):
+        """The [C + 1, C] counts of ops.eval_accumulate (row C: the rows labelled -1) as the square matrix sklearn's confusion_matrix builds:
+        one class per label present in y_true or y_pred, in np.union1d's order (-1 first)."""
+        import numpy as np
+        cm = np.asarray(cm, np.int64)
+        C = cm.shape[1]
+        assert cm.shape == (C + 1, C)
+        full = np.zeros((C + 1, C + 1), dtype=np.int64)
+        full[0, 1:], full[1:, 1:] = cm[C], cm[:C]
+        present = (full.sum(1) + full.sum(0)) > 0
+        return full[present][:, present]
+
+    @staticmethod
+    def metrics_from_confusion(cm):
+        """``classification_metrics(y_true, y_pred)`` from the counts alone: ``cm`` is the integer [C + 1, C] matrix of ops.eval_accumulate
+        (cm[t, p] rows with label t predicted p; row C holds the rows labelled -1, which sklearn counts as one more class of y_true).
+        Same label set (the union of the labels present in y_true or y_pred, -1 first), same zero rules, same order of the sums."""
+        import numpy as np
+        full = AlgorithmBase._present_confusion(cm)
+        tp, sup, prd = np.diag(full).astype(np.float64), full.sum(1).astype(np.float64), full.sum(0).astype(np.float64)
+        rec = np.divide(tp, sup, out=np.zeros_like(tp), where=sup > 0)
+        prec = np.divide(tp, prd, out=np.zeros_like(tp), where=prd > 0)
+        f1 = np.divide(2 * prec * rec, prec + rec, out=np.zeros_like(tp), where=(prec + rec) > 0)
+        return {"top-1-acc": float(tp.sum() / max(int(full.sum()), 1)), "balanced_acc": float(rec[sup > 0].mean()),
+                "precision": float(prec.mean()), "recall": float(rec.mean()), "F1": float(f1.mean())}
+
     def evaluate(self, eval_dest="eval", out_key="logits", return_logits=False, loader=None):
         """Inference over ``loader_dict[eval_dest]`` (or ``loader``: an iterable of {'x_lb', 'y_lb'}) with the EMA weights
         (``ema.apply_shadow`` of the reference == evaluating ``ema_model`` here), same result keys.  The forward runs on the
         inference kernels of the training path; predictions stay on the device until ONE copy at the end (the reference
-        synchronises three times per batch)."""
-        import numpy as np
+        synchronises three times per batch).  ``device_eval: True``: the loss and the confusion counts are accumulated on the device instead
+        (``_evaluate_on_device``), same keys and values."""
         assert out_key == "logits"
         self._invalidate_step_timing()
         net = self.ema_model
@@ -316,21 +352,34 @@ class AlgorithmBase:
         was_training = getattr(net, "training", True)
         net.training = False                          # BatchNorm backbones: running statistics (model.eval(), :381)
         loader = loader if loader is not None else self.loader_dict[eval_dest]
+        try:
+            run = self._evaluate_on_device if self.device_eval else self._evaluate_on_host
+            return run(net, loader, eval_dest, return_logits)
+        finally:
+            net.training = was_training
+
+    def _eval_batches(self, net, loader):
+        """(logits, labels) of every batch of ``loader`` on the device: the inference forward of the training path."""
+        for data in loader:
+            x = data["x_lb"]
+            if isinstance(x, dict):                                          # usb_nlp: {'input_ids', 'attention_mask'} (nlp_collactor.py:73)
+                from ..nets.bert import TokenBatch
+                x = TokenBatch.from_dict(x, self.device)
+            else:
+                x = x.to(self.device, non_blocking=True).contiguous()
+            y = data["y_lb"].to(self.device, non_blocking=True).contiguous()
+            lg, _, _ = net.forward_features(x, None, None, save=False)
+            yield lg, y
+
+    def _evaluate_on_host(self, net, loader, eval_dest, return_logits):
+        """Every batch's logits are kept; argmax, one copy and the metrics at the end."""
         C = self.num_classes
         logits_all, y_all = [], []
         loss_sum = torch.zeros(1, dtype=torch.float32, device=self.device)
         total = 0
         with ops.stream_scope():
-            for data in loader:
-                x = data["x_lb"]
-                if isinstance(x, dict):                                      # usb_nlp: {'input_ids', 'attention_mask'} (nlp_collactor.py:73)
-                    from ..nets.bert import TokenBatch
-                    x = TokenBatch.from_dict(x, self.device)
-                else:
-                    x = x.to(self.device, non_blocking=True).contiguous()
-                y = data["y_lb"].to(self.device, non_blocking=True).contiguous()
+            for lg, y in self._eval_batches(net, loader):
                 B = int(y.shape[0])
-                lg, _, _ = net.forward_features(x, None, None, save=False)
                 w = (y >= 0).to(torch.float32)                               # F.cross_entropy(ignore_index=-1): mean over the kept rows
                 loss = torch.empty(1, dtype=torch.float32, device=self.device)
                 ops.masked_ce(lg, y.clamp_min(0), w, None, 1.0, loss, torch.empty(B, C, dtype=torch.float32, device=self.device), B, C)
@@ -338,7 +387,6 @@ class AlgorithmBase:
                 logits_all.append(lg)
                 y_all.append(y)
                 total += B
-        net.training = was_training
         logits = torch.cat(logits_all)
         y_true = torch.cat(y_all).cpu().numpy()
         y_pred = logits.argmax(dim=-1).cpu().numpy()
@@ -347,6 +395,29 @@ class AlgorithmBase:
         out.update({eval_dest + "/" + k: v for k, v in m.items()})
         if return_logits:
             out[eval_dest + "/logits"] = logits.cpu().numpy()
+        return out
+
+    def _evaluate_on_device(self, net, loader, eval_dest, return_logits):
+        """``device_eval: True``: per batch ONE launch (ops.eval_accumulate) adds the batch's loss term and its confusion counts to device
+        accumulators; the end copies (C + 1) * C integers and the state instead of every batch's logits."""
+        import numpy as np
+        C = self.num_classes
+        block, state, confusion = ops.eval_accumulator(C, self.device)
+        logits_all = []
+        with ops.stream_scope():
+            for lg, y in self._eval_batches(net, loader):
+                ops.eval_accumulate(lg, y.long(), confusion, state)
+                if return_logits:
+                    logits_all.append(lg)
+        cm, loss_sum, _, rows, _ = ops.eval_accumulator_read(block, C)
+        ops.check_label_errors()                                             # a label outside [-1, C): F.cross_entropy raises (:407)
+        full = self._present_confusion(cm)
+        with np.errstate(invalid="ignore", divide="ignore"):                 # sklearn's confusion_matrix(normalize="true"): 0 for a class without true rows
+            self.print_fn("confusion matrix:\n" + np.array_str(np.nan_to_num(full / full.sum(axis=1, keepdims=True))))
+        out = {eval_dest + "/loss": loss_sum / max(rows, 1)}
+        out.update({eval_dest + "/" + k: v for k, v in self.metrics_from_confusion(cm).items()})
+        if return_logits:
+            out[eval_dest + "/logits"] = torch.cat(logits_all).cpu().numpy()
         return out
 
     # ---- checkpoints (algorithmbase.py:459-547) ----------------------------------------------------------

@@ -3,9 +3,14 @@
   Hook / priorities        semilearn/core/hooks/hook.py, priority.py
   ParamUpdateHook          semilearn/core/hooks/param_update.py:21-45
   EMAHook                  semilearn/core/hooks/ema.py:9-24
+  EvaluationHook           semilearn/core/hooks/evaluation.py     }
+  CheckpointHook           semilearn/core/hooks/checkpoint.py     }  registered with ``run_hooks: True`` (AlgorithmBase.set_hooks)
+  LoggingHook              semilearn/core/hooks/logging.py        }
 The backbone backward is fused into train_step (SURVEY.md 8(b) "Return"), so ParamUpdateHook here only
 all-reduces the flat gradient block (data parallel) and runs the fused AdamW / scheduler / zero_grad launch.
 """
+import os
+
 import torch
 
 PRIORITIES = {"HIGHEST": 0, "VERY_HIGH": 10, "HIGH": 30, "ABOVE_NORMAL": 40, "NORMAL": 50, "BELOW_NORMAL": 60,
@@ -28,8 +33,17 @@ class Hook:
     def after_train_epoch(self, algorithm): pass
     def after_run(self, algorithm): pass
 
+    def every_n_epochs(self, algorithm, n):
+        return (algorithm.epoch + 1) % n == 0 if n > 0 else False
+
     def every_n_iters(self, algorithm, n):
         return (algorithm.it + 1) % n == 0 if n > 0 else False
+
+    def is_last_epoch(self, algorithm):
+        return algorithm.epoch + 1 == algorithm.epochs
+
+    def is_last_iter(self, algorithm):
+        return algorithm.it + 1 == algorithm.num_train_iter
 
 
 class DeferredElapsed:
@@ -132,3 +146,76 @@ class DistSamplerSeedHook(Hook):
             loader = (algorithm.loader_dict or {}).get(name)
             if hasattr(loader, "set_epoch"):
                 loader.set_epoch(algorithm.epoch)
+
+
+def _writes_files(algorithm):
+    """The rank that writes checkpoints and log lines: every process of a single-process run, the first rank of each node otherwise."""
+    return not algorithm.distributed or algorithm.rank % algorithm.ngpus_per_node == 0
+
+
+def _save_path(algorithm):
+    return os.path.join(algorithm.save_dir, algorithm.save_name)
+
+
+class EvaluationHook(Hook):
+    """core/hooks/evaluation.py: ``evaluate('eval')`` every num_eval_iter steps and at the last one, its results merged into log_dict, the best
+    top-1 accuracy (strictly greater) and its iteration kept.  after_run: latest_model.pth, the test accuracy of model_best.pth when there is
+    a test loader, ``algorithm.results_dict``.  One deviation: when no evaluation ever improved on 0 there is no model_best.pth -- the
+    reference's load raises; here one line says so and ``test/best_acc`` is left out."""
+
+    def after_train_step(self, algorithm):
+        if self.every_n_iters(algorithm, algorithm.num_eval_iter) or self.is_last_iter(algorithm):
+            algorithm.print_fn("validating...")
+            algorithm.log_dict.update(algorithm.evaluate("eval"))
+            if algorithm.log_dict["eval/top-1-acc"] > algorithm.best_eval_metric:
+                algorithm.best_eval_metric = algorithm.log_dict["eval/top-1-acc"]
+                algorithm.best_it = algorithm.it
+
+    def after_run(self, algorithm):
+        if _writes_files(algorithm):
+            algorithm.save_model("latest_model.pth", _save_path(algorithm))
+        results_dict = {"eval/best_acc": algorithm.best_eval_metric, "eval/best_it": algorithm.best_it}
+        if "test" in (algorithm.loader_dict or {}):
+            best_model_path = os.path.join(_save_path(algorithm), "model_best.pth")
+            if os.path.exists(best_model_path):
+                algorithm.load_model(best_model_path)
+                results_dict["test/best_acc"] = algorithm.evaluate("test")["test/top-1-acc"]
+            else:
+                algorithm.print_fn("no model_best.pth under %s (no evaluation improved on 0): test/best_acc is not computed" % _save_path(algorithm))
+        algorithm.results_dict = results_dict
+
+
+class CheckpointHook(Hook):
+    """core/hooks/checkpoint.py: latest_model.pth at the evaluation cadence, then model_best.pth when this iteration is the best one (it runs
+    after EvaluationHook)."""
+
+    def after_train_step(self, algorithm):
+        if self.every_n_iters(algorithm, algorithm.num_eval_iter) or self.is_last_iter(algorithm):
+            if _writes_files(algorithm):
+                algorithm.save_model("latest_model.pth", _save_path(algorithm))
+                if algorithm.it == algorithm.best_it:
+                    algorithm.save_model("model_best.pth", _save_path(algorithm))
+
+
+class LoggingHook(Hook):
+    """core/hooks/logging.py: one line with every log_dict entry at the evaluation cadence (with the best accuracy so far) or else at the
+    logging cadence, and the same entries to ``tb_log``.  The deferred log scalars (DeferredScalar, DeferredElapsed) synchronise here."""
+
+    @staticmethod
+    def _entries(algorithm):
+        items = list(algorithm.log_dict.items())
+        return "".join("{:s}: {:.4f}".format(k, v) + (", " if i != len(items) - 1 else " ") for i, (k, v) in enumerate(items))
+
+    def after_train_step(self, algorithm):
+        at_eval = self.every_n_iters(algorithm, algorithm.num_eval_iter)
+        if not at_eval and not self.every_n_iters(algorithm, algorithm.num_log_iter):
+            return
+        if _writes_files(algorithm):
+            if at_eval:
+                text = f"{algorithm.it + 1} iteration, USE_EMA: {algorithm.ema_m != 0}, " + self._entries(algorithm)
+                text += "BEST_EVAL_ACC: {:.4f}, at {:d} iters".format(algorithm.best_eval_metric, algorithm.best_it + 1)
+            else:
+                text = f"{algorithm.it + 1} iteration USE_EMA: {algorithm.ema_m != 0}, " + self._entries(algorithm)
+            algorithm.print_fn(text)
+        if algorithm.tb_log is not None:
+            algorithm.tb_log.update({k: float(v) for k, v in algorithm.log_dict.items()}, algorithm.it)

@@ -171,6 +171,9 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// address of the label-range error word on the current device (rewarder.hip, read by srhip_label_error)
+int* sr_label_err_ptr();
+
 // Tuning switches (tile splits, knock-outs, schedule variants for tools/microbench.py and the A/B scripts) exist in the tuning build only
 // (SRHIP_TUNING_BUILD=1 -> -DSRHIP_TUNING).  The shipped library reads two environment variables, both test hooks: SRHIP_GEMM = tile | small | big256 | big128 | big2wg (force that
 // kernel), bigold (the lockstep 256 x 256 kernel wherever the plan says 256 x 256), bigoldf (forced), big256r8 (eight-slot ring) (pins the GEMM

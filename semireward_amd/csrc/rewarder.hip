@@ -145,7 +145,7 @@ __global__ void transpose_small_kernel(const float* __restrict__ W, float* __res
 // 180-181).  A kernel cannot raise: it records the event in this word and stays memory safe (embedding row 0 is read, the scatter is skipped);
 // the host fetches the word with srhip_label_error() at its next synchronisation point and raises there.
 // bit 0: embedding lookup out of range, bit 1: embedding-gradient scatter out of range, bit 2: generator output not representable (NaN / >= 2^63),
-// bit 3: one_hot class out of range in the SR target
+// bit 3: one_hot class out of range in the SR target, bit 4: evaluation label outside [-1, C) (eval.hip)
 __device__ int srhip_label_err;
 
 // Kernel 1: a tile of 8 feature rows AND the matching 8 label rows of one group.
@@ -606,6 +606,14 @@ extern "C" int srhip_generator_fwd(const float* params, const float* params_t, c
   SR_LAUNCH(generator_kernel, dim3(cdiv(B, RT)), dim3(256), sm, (hipStream_t)stream, params, params_t, x, out, label, B, F);
   SR_CHECK_LAUNCH();
   return SR_OK;
+}
+
+// address of the word on the CURRENT device, for the kernels of other translation units that record into it (eval.hip); NULL if the lookup
+// fails.  Resolved at every call, as srhip_label_error does: a process may drive more than one device.
+int* sr_label_err_ptr() {
+  int* p = nullptr;
+  if (hipGetSymbolAddress((void**)&p, HIP_SYMBOL(srhip_label_err)) != hipSuccess) return nullptr;
+  return p;
 }
 
 extern "C" int srhip_label_error(int* bits_out, int reset, void* stream) {

@@ -889,6 +889,40 @@ def consistency_l1(logits, targets, mask, mask2, grad_scale, reduction, loss_row
     _soft_criterion("srhip_consistency_l1", logits, targets, mask, mask2, grad_scale, reduction, loss_rows, loss_out, dlogits, B, C)
 
 
+# ---- evaluation accumulators ----------------------------------------------------------------------
+EVAL_STATE_WORDS = 8          # srhip_eval_accumulate's state {double loss_sum, nll_sum; int64 rows, kept} in int32 words
+
+
+def eval_accumulator(C, device):
+    """A zeroed int32 block [8 + (C + 1) * C] holding the state and the confusion matrix of srhip_eval_accumulate side by side, so that ONE
+    copy brings both to the host: returns (block, state view, confusion view [C + 1, C])."""
+    block = torch.zeros(EVAL_STATE_WORDS + (C + 1) * C, dtype=torch.int32, device=device)
+    return block, block[:EVAL_STATE_WORDS], block[EVAL_STATE_WORDS:].view(C + 1, C)
+
+
+def eval_accumulator_read(block, C):
+    """The block of eval_accumulator on the host (one transfer, synchronises): (confusion int32 [C + 1, C], loss_sum, nll_sum, rows, kept)."""
+    import numpy as np
+    h = block.cpu().numpy()
+    st = h[:EVAL_STATE_WORDS]
+    f, n = st.view(np.float64), st.view(np.int64)
+    return h[EVAL_STATE_WORDS:].reshape(C + 1, C), float(f[0]), float(f[1]), int(n[2]), int(n[3])
+
+
+def eval_accumulate(logits, y, confusion, state, pred_out=None, row_offset=0):
+    """One evaluation batch into the device accumulators (srhip_eval_accumulate): logits fp32 [B, C] (rows may be strided), y int64 [B];
+    confusion int32 [C + 1, C] and state (8 int32 words, 8-byte aligned) are the caller's and start at zero; pred_out int64 (optional)
+    receives the predictions at row_offset .. row_offset + B - 1."""
+    z, ld = _rows(logits)
+    B, C = int(logits.shape[0]), int(logits.shape[1])
+    if _CHECK_ARGS:
+        assert y.dtype == torch.int64 and y.numel() == B
+        assert confusion.dtype == torch.int32 and confusion.numel() == (C + 1) * C
+        assert state.dtype == torch.int32 and state.numel() == EVAL_STATE_WORDS
+        assert pred_out is None or (pred_out.dtype == torch.int64 and 0 <= row_offset and row_offset + B <= pred_out.numel())
+    _call("srhip_eval_accumulate", z, ld, _p(y), _p(confusion), _p(state), _p(pred_out), row_offset, B, C, _s())
+
+
 # ---- rewarder / generator ---------------------------------------------------------------------
 def rewarder_param_count(F, L):
     return int(_lib.lib().srhip_rewarder_param_count(F, L))
@@ -944,7 +978,8 @@ def sr_target(gen, ref, target, B, num_classes=0):
 _LABEL_ERR = ("a label outside [0, label_dim) reached the rewarder's nn.Embedding (semireward.py:57)",
               "a label outside [0, label_dim) reached the embedding gradient (semireward.py:57)",
               "the generator output is NaN or not representable as int64 (srflexmatch.py:158-159)",
-              "a label outside [0, num_classes) reached F.one_hot of the SR target (srflexmatch.py:180-181, :195-196)")
+              "a label outside [0, num_classes) reached F.one_hot of the SR target (srflexmatch.py:180-181, :195-196)",
+              "an evaluation label outside [-1, num_classes) reached F.cross_entropy (algorithmbase.py:407)")
 
 
 def check_label_errors(reset=True):
