@@ -669,6 +669,23 @@ int srhip_augment(const unsigned char* src, int n_src, int H0, int W0, int B, in
 int srhip_resize_bilinear_u8(const unsigned char* src, int N, int H0, int W0, unsigned char* dst, int S, const int* bounds, const int* coefs,
                              int ksize, unsigned char* tmp, void* stream);
 
+/* ---- one view of a waveform batch from the device-resident clip store (``device_audio: True``, semireward_amd/data/device_audio.py):
+ * random_subsample's window (semilearn/datasets/utils.py:177-183, the offset drawn on the host), the collator's zero padding to S samples and
+ * Wav2Vec2FeatureExtractor's normalisation without an attention mask (audio_collactor.py:61-83), one launch.
+ *   store    fp32, every clip starts at a multiple of 4 floats;  row_off int64 [n_rows] first float of a clip, row_len int32 [n_rows] its samples
+ *   src_row  int64 [B] store row of output row b;  crop_off int32 [B] first sample of its window
+ *   out      fp32 [B, ldo], 16-byte aligned, ldo % 4 == 0, ldo >= S; columns S .. ldo are not written
+ * With r = src_row[b], n = min(row_len[r] - crop_off[b], S): v[t] = store[row_off[r] + crop_off[b] + t] for t < n, 0 for n <= t < S (a row or an
+ * offset outside the store gives n = 0: the kernel never reads past a row; the Python wrapper refuses such arguments on the host).
+ *   normalize = 0: out[b, t] = v[t], bit for bit.
+ *   normalize = 1: m = sum(v) / S, var = sum((v - m)^2) / S over all S positions, out[b, t] = (v[t] - m) / sqrt(var + 1e-7) -- the padded
+ *                  positions too (they become -m / sqrt(var + 1e-7)).  Two passes in fp64 with a fixed reduction order and no atomics
+ *                  (run-to-run bit-identical); an element is one fp32 rounding of the float64 value.
+ * One workgroup per row.  SR_EINVAL: a null pointer, n_rows <= 0, B <= 0, B > 65535, S <= 0, S > 2^30, ldo < S, ldo % 4, out not 16-byte
+ * aligned, normalize not 0 / 1. */
+int srhip_wave_view(const float* store, const long long* row_off, const int* row_len, int n_rows, const long long* src_row,
+                    const int* crop_off, int B, int S, int normalize, float* out, int ldo, void* stream);
+
 /* ---- WideResNet building blocks (classic_cv backbone, semilearn/nets/wrn/wrn.py; BASELINE.json configs[0], parity configuration) ----
  * Feature maps are NHWC = row-major [rows = B*H*W, C].  conv = im2col (bf16) + srhip_gemm_nt; dW = srhip_gemm_tn_grouped_f32(dY, col);
  * dX = srhip_gemm_nt(dY, W^T) + col2im.

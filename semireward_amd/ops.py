@@ -1436,3 +1436,38 @@ def resize_bilinear_u8(src, S, chunk=4096):
         n = min(chunk, N - s)
         _call("srhip_resize_bilinear_u8", _p(src[s:s + n]), n, H0, W0, _p(dst[s:s + n]), S, _p(bounds), _p(coefs), ksize, _p(tmp), _s())
     return dst
+
+
+def check_wave_rows(src_row, crop_off, row_len):
+    """The host-side argument check of ``wave_view``: numpy ``src_row`` / ``crop_off`` (where a loader produces them) against the numpy
+    ``row_len`` of the store.  The kernel clamps such a row to an empty window; here it is an error."""
+    import numpy as np
+    src_row, crop_off = np.asarray(src_row), np.asarray(crop_off)
+    if src_row.shape != crop_off.shape or src_row.ndim != 1:
+        raise ValueError("wave_view: src_row and crop_off must be 1-D arrays of one length, got %s and %s" % (src_row.shape, crop_off.shape))
+    if src_row.size and (src_row.min() < 0 or src_row.max() >= len(row_len)):
+        raise IndexError("wave_view: src_row outside the store's %d rows" % len(row_len))
+    if src_row.size and (crop_off.min() < 0 or (crop_off >= np.asarray(row_len)[src_row]).any()):
+        raise IndexError("wave_view: crop_off outside its clip (0 <= crop_off < row_len[src_row])")
+
+
+def wave_view(store, row_off, row_len, src_row, crop_off, S, normalize, host=None):
+    """One view of a batch from the flat fp32 clip store (srhip.h: srhip_wave_view): row b is S samples of clip ``src_row[b]`` from sample
+    ``crop_off[b]``, zero-padded, normalised like Wav2Vec2FeatureExtractor when ``normalize``.  store fp32, row_off int64, row_len int32,
+    src_row int64 [B], crop_off int32 [B], all on the device -> new fp32 [B, S] (a view of a [B, ldo] allocation, ldo = S rounded up to 4:
+    contiguous when S % 4 == 0).  ``host``: (src_row, crop_off, row_len) as numpy arrays, checked before the launch (check_wave_rows)."""
+    if store.dtype != torch.float32 or row_off.dtype != torch.int64 or row_len.dtype != torch.int32:
+        raise ValueError("wave_view: the store is fp32 with int64 row_off and int32 row_len, got %s / %s / %s" % (store.dtype, row_off.dtype, row_len.dtype))
+    if src_row.dtype != torch.int64 or crop_off.dtype != torch.int32 or src_row.dim() != 1 or src_row.shape != crop_off.shape:
+        raise ValueError("wave_view: src_row is int64 [B] and crop_off int32 [B], got %s %s / %s %s"
+                         % (src_row.dtype, tuple(src_row.shape), crop_off.dtype, tuple(crop_off.shape)))
+    if row_off.shape != row_len.shape or row_off.dim() != 1:
+        raise ValueError("wave_view: row_off and row_len hold one entry per clip")
+    if host is not None:
+        check_wave_rows(*host)
+    B, S = int(src_row.shape[0]), int(S)
+    ldo = (S + 3) & ~3
+    out = torch.empty(B, ldo, dtype=torch.float32, device=store.device)
+    _call("srhip_wave_view", _p(store), _p(row_off), _p(row_len), int(row_len.shape[0]), _p(src_row), _p(crop_off), B, S, 1 if normalize else 0,
+          _p(out), ldo, _s())
+    return out if ldo == S else out[:, :S]
