@@ -686,6 +686,22 @@ int srhip_resize_bilinear_u8(const unsigned char* src, int N, int H0, int W0, un
 int srhip_wave_view(const float* store, const long long* row_off, const int* row_len, int n_rows, const long long* src_row,
                     const int* crop_off, int B, int S, int normalize, float* out, int ldo, void* stream);
 
+/* ---- one view of a token batch from the device-resident token store (``device_tokens: True``, semireward_amd/data/device_tokens.py): the
+ * collator's ``tokenizer.pad(padding=True)`` (nlp_collactor.py:63-110) on rows tokenised once, and the lengths srhip_mask_lengths would
+ * recover from its attention mask, one launch.
+ *   store    int32, 16-byte aligned, every row starts at a multiple of 4 ints (a row_off that is no multiple of 4 is still read correctly,
+ *            with single loads instead of 16-byte ones);  row_off int64 [n_rows] first int of a row, row_len int32
+ *            [n_rows] its tokens;  src_row int64 [B] store row of output row b
+ *   ids      int64 [B, ld_ids] (what srhip_embed_ln_fwd takes), ld_ids >= L; columns L .. ld_ids are not written;  key_len int32 [B]
+ * With r = src_row[b], n = min(row_len[r], L): ids[b, t] = store[row_off[r] + t] for t < n, pad_id for n <= t < L, key_len[b] = n (a row
+ * longer than L is truncated: key_len = L).  A src_row outside [0, n_rows) gives n = 0: an all-pad row, nothing read (the Python wrapper
+ * refuses such a row on the host).  The kernel never reads past a row: quads inside a row are aligned 16-byte loads, the quad holding the
+ * row's end is peeled.  16-byte stores where the output address allows (ld_ids even), 8-byte stores otherwise.  One workgroup per row, no
+ * LDS, no atomics.  SR_EINVAL: a null pointer, n_rows <= 0, B <= 0, B > 65535, L <= 0, ld_ids < L, store not 16-byte aligned,
+ * ids not 8-byte aligned. */
+int srhip_token_view(const int* store, const long long* row_off, const int* row_len, int n_rows, const long long* src_row, int B, int L,
+                     int pad_id, long long* ids, int ld_ids, int* key_len, void* stream);
+
 /* ---- WideResNet building blocks (classic_cv backbone, semilearn/nets/wrn/wrn.py; BASELINE.json configs[0], parity configuration) ----
  * Feature maps are NHWC = row-major [rows = B*H*W, C].  conv = im2col (bf16) + srhip_gemm_nt; dW = srhip_gemm_tn_grouped_f32(dY, col);
  * dX = srhip_gemm_nt(dY, W^T) + col2im.

@@ -104,6 +104,7 @@ class AlgorithmBase:
         self.ema = None
         self.device_data = bool(g("device_data", False))     # dataset arrays resident in HBM, loaders of data/device_loader.py
         self.device_audio = bool(g("device_audio", False))   # waveform clips resident in HBM, loaders of data/device_audio.py (usb_audio)
+        self.device_tokens = bool(g("device_tokens", False)) # token rows resident in HBM, loaders of data/device_tokens.py (usb_nlp)
         self.device_eval = bool(g("device_eval", False))     # evaluate() accumulates loss and confusion matrix on the device (csrc/eval.hip)
         self.run_hooks = bool(g("run_hooks", False))         # the reference's EvaluationHook / CheckpointHook / LoggingHook join the hook list
         self.dataset_dict = self.set_dataset()
@@ -115,6 +116,9 @@ class AlgorithmBase:
         if self.device_audio:
             from ..data.device_audio import refuse_unsupported_model as refuse_unsupported_audio_model
             refuse_unsupported_audio_model(self.model)
+        if self.device_tokens:               # a ValueError before any launch: max_length beyond max_pos, a stored id beyond the vocabulary
+            from ..data.device_tokens import refuse_unsupported_model as refuse_unsupported_token_model
+            refuse_unsupported_token_model(self.model, self.dataset_dict)
         if self.model.couples_batch_rows:
             self.model.dp = self.dp          # BatchNorm backbone under data parallel = SyncBatchNorm, as the reference's send_model_cuda (misc.py:55)
         self.ema_model = self.set_ema_model()
@@ -125,7 +129,7 @@ class AlgorithmBase:
         self._hooks = []
         self.hooks_dict = OrderedDict()
         self.set_hooks()
-        if self.device_data or self.device_audio:      # the reference's DistSamplerSeedHook (algorithmbase.py:565); every other configuration keeps its hook list
+        if self.device_data or self.device_audio or self.device_tokens:      # the reference's DistSamplerSeedHook (algorithmbase.py:565); every other configuration keeps its hook list
             self.register_hook(DistSamplerSeedHook(), None, "NORMAL")
 
     def init(self, **kwargs):
@@ -138,6 +142,9 @@ class AlgorithmBase:
         reference's rank-0-first barriers and its ``ulb_dest_len`` / ``lb_dest_len`` side effects on ``args``.  ``args.dataset_dict``: a ready
         dict is taken as is.  Otherwise None -- ``train(batches=...)`` or a ``loader_dict`` assigned by the caller feeds the loop."""
         a = self.args
+        if self.device_tokens:                # refused from the yaml keys, before a dataset is looked at (first: it names a sibling key set beside it)
+            from ..data.device_tokens import refuse_unsupported as refuse_unsupported_tokens
+            refuse_unsupported_tokens(a)
         if self.device_audio:                 # refused from the yaml keys, before a dataset is looked at
             from ..data.device_audio import refuse_unsupported as refuse_unsupported_audio
             refuse_unsupported_audio(a)
@@ -151,6 +158,10 @@ class AlgorithmBase:
                 raise RuntimeError("device_audio: True needs the clips: pass args.dataset_dict (reference dataset objects, or plain "
                                    "{'data': [1-D float arrays], 'targets': ..., 'data_s': [[...], ...]} dicts), or install semilearn so that its "
                                    "get_dataset runs")
+            if self.device_tokens:
+                raise RuntimeError("device_tokens: True needs the sentences: pass args.dataset_dict (reference dataset objects, or plain "
+                                   "{'data': [strings or 1-D token arrays], 'targets': ..., 'data_s': [[...], [...]]} dicts), or install semilearn "
+                                   "so that its get_dataset runs")
             return None
         if ready is None:
             if self.rank != 0 and self.distributed:
@@ -165,6 +176,9 @@ class AlgorithmBase:
         if self.device_audio:                 # float clips -> one flat fp32 store in HBM
             from ..data.device_audio import build_wave_datasets
             ready = build_wave_datasets(a, ready, self.device)
+        if self.device_tokens:                # sentences and variants, tokenised once -> one flat int32 store in HBM
+            from ..data.device_tokens import build_token_datasets
+            ready = build_token_datasets(a, ready, self.device)
         a.ulb_dest_len = len(ready["train_ulb"]) if ready.get("train_ulb") is not None else 0
         a.lb_dest_len = len(ready["train_lb"])
         self.print_fn("unlabeled data number: {}, labeled data number {}".format(a.ulb_dest_len, a.lb_dest_len))
@@ -190,6 +204,13 @@ class AlgorithmBase:
             self.print_fn("Create device-resident waveform train and test data loaders")
             ld = build_wave_loaders(a, self.dataset_dict, list(signature(self.train_step).parameters), self.num_train_iter, self.epochs,
                                     self.world_size if self.distributed else 1, self.rank if self.distributed else 0, self.print_fn)
+            self.print_fn(f"[!] data loader keys: {ld.keys()}")
+            return ld
+        if self.device_tokens:
+            from ..data.device_tokens import build_token_loaders
+            self.print_fn("Create device-resident token train and test data loaders")
+            ld = build_token_loaders(a, self.dataset_dict, list(signature(self.train_step).parameters), self.num_train_iter, self.epochs,
+                                     self.world_size if self.distributed else 1, self.rank if self.distributed else 0)
             self.print_fn(f"[!] data loader keys: {ld.keys()}")
             return ld
         get_data_loader = (getattr(a, "data_functions", None) or reference_data_functions())[1]
@@ -386,6 +407,8 @@ class AlgorithmBase:
             if isinstance(x, dict):                                          # usb_nlp: {'input_ids', 'attention_mask'} (nlp_collactor.py:73)
                 from ..nets.bert import TokenBatch
                 x = TokenBatch.from_dict(x, self.device)
+            elif hasattr(x, "key_len"):                                      # a TokenBatch of the device token loaders: taken as it is
+                x = x.to(self.device, non_blocking=True)
             else:
                 x = x.to(self.device, non_blocking=True).contiguous()
             y = data["y_lb"].to(self.device, non_blocking=True).contiguous()

@@ -139,7 +139,7 @@ class EMAHook(Hook):
 
 class DistSamplerSeedHook(Hook):
     """core/hooks/sampler_seed.py of the reference: every epoch reshuffles the train samplers with the epoch as the seed.  Registered only when
-    the device loaders feed the loop (``device_data: True`` / ``device_audio: True``); they re-seed their augmentation draws with the epoch at the same moment."""
+    the device loaders feed the loop (``device_data: True`` / ``device_audio: True`` / ``device_tokens: True``); they re-seed their augmentation draws with the epoch at the same moment."""
 
     def before_train_epoch(self, algorithm):
         for name in ("train_lb", "train_ulb"):

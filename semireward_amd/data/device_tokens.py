@@ -1,0 +1,351 @@
+"""Device-resident token store and loaders of the usb_nlp configurations (``device_tokens: True``): every sentence and every augmented variant
+is tokenised ONCE and lives in HBM in one flat int32 array, the reference's sampler decides which sentences form a batch, and a view of a
+batch -- gather, right-pad with [PAD] to the batch's longest row, int64 ids, the lengths -- is one srhip_token_view launch
+(csrc/token_view.hip).  No tokenizer in the step, no worker processes, no per-step host-to-device copy, no srhip_mask_lengths launch: the
+loaders hand ``nets.bert.TokenBatch`` objects to the step.
+
+Restates
+  semilearn/datasets/nlp_datasets/datasetbase.py:43-81     which keys a labelled / unlabelled sample carries; 'text_s' is one of the two variants
+  semilearn/datasets/collactors/nlp_collactor.py:49-61     tokenizer(text, max_length=max_length, truncation=True, padding=False)['input_ids']
+  semilearn/datasets/collactors/nlp_collactor.py:63-110    tokenizer.pad(padding=True): every view right-padded to ITS OWN batch's longest row
+  semilearn/datasets/samplers/sampler.py:55-73             the epoch's index stream (EpochSampler of data/device_loader.py, unchanged)
+One deviation, documented in configs/README.md: the reference picks the strong variant with an unseeded ``random.randint(1, 2)`` in every
+worker process; here the pick comes from a numpy generator seeded with (seed, rank, loader role, epoch), so the draws cannot be matched.  The
+sampler stream, the tokenisation and the padding are matched exactly (tests/golden/device_tokens.npz)."""
+import os
+
+import numpy as np
+import torch
+
+from .. import ops
+from .device_loader import ROLES, EpochSampler
+
+HUB_NAMES = {"bert_base_uncased": "bert-base-uncased", "bert_base_cased": "bert-base-cased"}     # the reference's collators (nlp_collactor.py:113-122)
+TOKENIZER_FILES = ("tokenizer.json", "vocab.txt")
+DATA_S_HELP = ("give the unlabelled set the augmented variants of every sentence as {'data': [...], 'data_s': [[variant 0 of every sentence], "
+               "[variant 1 ...]]} (the reference's (ori, aug_0, aug_1) triples: its back-translations)")
+
+
+def _h2d(t, device):
+    """Every host-to-device copy of the loaders goes through here (one per epoch and train loader; the tests count them)."""
+    return t.to(device)
+
+
+def _rows(data, what, tokenize, max_length):
+    """A list of strings / 1-D integer arrays -> list of contiguous int32 arrays, each refusal with its reason."""
+    out = []
+    for i, s in enumerate(data):
+        if isinstance(s, str):
+            if tokenize is None:
+                raise ValueError("device_tokens: row %d of %s is a string and no tokenizer was given (pass tokenize=, or already-tokenised "
+                                 "1-D integer arrays)" % (i, what))
+            s = np.asarray(tokenize(str(s)), dtype=np.int64)                # truncated to max_length by the tokenizer, [SEP] kept last
+        else:
+            s = s.detach().cpu().numpy() if torch.is_tensor(s) else np.asarray(s)
+            if s.dtype.kind not in "iu":
+                raise ValueError("device_tokens needs strings or already-tokenised integer arrays, got dtype %s for row %d of %s" % (s.dtype, i, what))
+        if s.ndim != 1:
+            raise ValueError("device_tokens needs 1-D token rows, got shape %s for row %d of %s" % (s.shape, i, what))
+        if s.size == 0:
+            raise ValueError("device_tokens: row %d of %s is empty (a tokenised sentence holds at least [CLS] [SEP])" % (i, what))
+        if max_length is not None and s.size > max_length:
+            raise ValueError("device_tokens: row %d of %s holds %d tokens, more than max_length = %d; the store does not truncate silently "
+                             "(truncate as the tokenizer does: keep [SEP] last)" % (i, what, s.size, max_length))
+        if s.min() < 0 or s.max() > np.iinfo(np.int32).max:
+            raise ValueError("device_tokens: row %d of %s holds a negative token id (or one past int32)" % (i, what))
+        out.append(np.ascontiguousarray(s, dtype=np.int32))
+    return out
+
+
+def _is_text(x):
+    return isinstance(x, str) or (isinstance(x, np.ndarray) and x.ndim == 0 and x.dtype.kind in "US")
+
+
+def _triples(data):
+    """The reference's (ori, aug_0, aug_1) string triples -> (sentences, [every aug_0, every aug_1]) as lists of str; None when ``data`` is
+    something else.  The evaluation sets keep the list of tuples json_data.py builds; the training sets went through split_ssl_data
+    (semilearn/datasets/utils.py:38-52: ``np.array(data)[idx]``) and are [n, 3] string arrays, whose rows are 1-D arrays of 3 strings."""
+    rows = list(data)
+    if not rows or not all(isinstance(t, (tuple, list, np.ndarray)) and not isinstance(t, str) and np.ndim(t) == 1 and len(t) == 3
+                           and all(_is_text(x) for x in t) for t in rows):
+        return None
+    return [str(t[0]) for t in rows], [[str(t[1 + v]) for t in rows] for v in range(2)]
+
+
+class DeviceTokenDataset:
+    """Token rows of any length in one flat int32 device array ``store``; row r occupies store[row_off[r] : row_off[r] + row_len[r]] and
+    starts at a multiple of 4 ints (the gap holds ``pad_id``).  Rows 0 .. n - 1 are the sentences; with ``data_s`` (V lists of n variants)
+    row n (1 + v) + i is variant v of sentence i (``strong_row``).  int64 targets resident too (None: unlabelled).  ``row_len_host`` /
+    ``row_off_host`` / ``targets_host`` keep numpy copies for the host side of a loader; ``max_id_host`` is the largest stored id, checked
+    against the model's vocabulary before anything is launched.  ``data`` items: strings (tokenised once, here, by ``tokenize``) or
+    already-tokenised 1-D integer arrays (refused when longer than ``max_length``)."""
+    pad_id = 0                                         # [PAD] of both reference vocabularies, BertConfig.pad_id
+
+    def __init__(self, data, targets, device, data_s=None, max_length=None, tokenize=None):
+        self.max_length = None if max_length is None else int(max_length)
+        rows = _rows(data, "data", tokenize, self.max_length)
+        self.n = len(rows)
+        if self.n == 0:
+            raise ValueError("device_tokens: the dataset holds no sentence")
+        self.n_variants = 0
+        if data_s is not None:
+            for v, var in enumerate(data_s):
+                var = _rows(var, "data_s[%d]" % v, tokenize, self.max_length)
+                if len(var) != self.n:
+                    raise ValueError("device_tokens: data_s[%d] must hold one variant of every sentence (%d), got %d" % (v, self.n, len(var)))
+                rows += var
+            self.n_variants = len(data_s)
+            if self.n_variants == 0:
+                raise ValueError("device_tokens: data_s is empty; " + DATA_S_HELP)
+        self.device = torch.device(device)
+        self.row_len_host = np.array([r.size for r in rows], dtype=np.int32)
+        padded = (self.row_len_host.astype(np.int64) + 3) & ~np.int64(3)
+        self.row_off_host = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
+        flat = np.full(int(padded.sum()), self.pad_id, dtype=np.int32)
+        for r, o in zip(rows, self.row_off_host):
+            flat[o:o + r.size] = r
+        self.max_id_host = int(max(int(r.max()) for r in rows))
+        self.store = torch.from_numpy(flat).to(self.device)
+        self.row_off = torch.from_numpy(self.row_off_host).to(self.device)
+        self.row_len = torch.from_numpy(self.row_len_host).to(self.device)
+        if targets is None:
+            self.targets = self.targets_host = None
+        else:
+            self.targets_host = np.asarray(targets.cpu() if torch.is_tensor(targets) else targets).astype(np.int64)
+            if self.targets_host.shape != (self.n,):
+                raise ValueError("targets must hold one label per sentence (%d sentences, targets of shape %s)" % (self.n, self.targets_host.shape))
+            self.targets = torch.from_numpy(self.targets_host).to(self.device)
+
+    @classmethod
+    def from_reference(cls, dset, device, tokenize=None, max_length=None):
+        """A reference nlp ``BasicDataset`` (``.data``: (ori, aug_0, aug_1) string triples -- a list of tuples, or the [n, 3] string array
+        split_ssl_data leaves in the training sets --, ``.targets``, ``.is_ulb``) or a plain
+        {'data': [...], 'targets': ..., 'data_s': [[...], [...]]} dict of strings / token arrays.  Evaluation sets carry the literal 'None'
+        as both augmentations (json_data.py:42): such variants are not stored."""
+        if isinstance(dset, cls):
+            return dset
+        if isinstance(dset, dict):
+            return cls(dset["data"], dset.get("targets"), device, dset.get("data_s"), max_length, tokenize)
+        ulb = bool(getattr(dset, "is_ulb", False))
+        data, data_s = list(dset.data), getattr(dset, "data_s", None)
+        tri = _triples(data)
+        if tri is not None:
+            data, var = tri
+            data_s = None if all(x == "None" for v in var for x in v) else var
+        return cls(data, None if ulb else getattr(dset, "targets", None), device, data_s, max_length, tokenize)
+
+    def strong_row(self, variant, index):
+        return self.n * (1 + np.asarray(variant, dtype=np.int64)) + np.asarray(index, dtype=np.int64)
+
+    def __len__(self):
+        return self.n
+
+
+def _view(ds, src_row, L):
+    from ..nets.bert import TokenBatch
+    return TokenBatch(*ops.token_view(ds.store, ds.row_off, ds.row_len, src_row, L, ds.pad_id))
+
+
+class TokenTrainLoader:
+    """Per-step dicts of one epoch: consecutive ``batch_size`` chunks of the sampler's stream (drop_last).  'idx_*' the dataset indices,
+    'y_*' the targets, 'x_*' the sentence and 'x_*_s' one of its variants, picked uniformly -- every view a ``TokenBatch`` right-padded to
+    the longest row of ITS OWN batch (the collator's ``padding=True``; the views of a step are NOT padded to a common length), one
+    srhip_token_view launch.  ``strong=False`` leaves the strong views out: not drawn, not launched.  The draws are a function of
+    (``seed``, epoch): ``set_epoch`` / iterating again replays them.  Everything an epoch needs -- its index stream, targets and store rows --
+    goes to the device in ONE copy when the epoch starts; the per-batch lengths are computed on the host from ``row_len_host`` (vectorised;
+    nothing is read back from the device).  ``draws`` keeps the host arrays of the last epoch started:
+    {view key: (store rows int64 [N], padded length of every batch int64 [len(self)])}."""
+
+    def __init__(self, dataset, batch_size, sampler, strong=True, keys=("idx_lb", "x_lb", "y_lb"), seed=(0,)):
+        self.dataset, self.batch_size, self.sampler = dataset, int(batch_size), sampler
+        self.keys = tuple(k for k in keys if strong or not self._is_strong(k))
+        if any(k.startswith("y") for k in self.keys) and dataset.targets is None:
+            raise ValueError("a loader with a target key needs a labelled dataset")
+        if any(self._is_strong(k) for k in self.keys) and dataset.n_variants == 0:
+            raise ValueError("device_tokens: a strong view was asked of a dataset without data_s; " + DATA_S_HELP)
+        self.seed = tuple(int(s) for s in seed)
+        self.epoch = 0
+        self.draws = {}
+
+    @staticmethod
+    def _is_strong(k):
+        return k.startswith("x") and k.endswith("_s")
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+        self.sampler.set_epoch(epoch)
+
+    def __len__(self):
+        return len(self.sampler) // self.batch_size
+
+    def _epoch_table(self):
+        """The epoch as one int64 host table [rows, N] and the meaning of its rows: {key: row} ('idx' / 'y': the values; views: the store rows)."""
+        ds, B, nb = self.dataset, self.batch_size, len(self)
+        self.sampler.set_epoch(self.epoch)
+        rng = np.random.Generator(np.random.PCG64(self.seed + (self.epoch,)))
+        stream = np.ascontiguousarray(self.sampler.indices(), dtype=np.int64)
+        N, rows, where, self.draws = stream.size, [], {}, {}
+        for k in self.keys:
+            where[k] = len(rows)
+            if k.startswith("idx"):
+                rows.append(stream)
+            elif k.startswith("y"):
+                rows.append(ds.targets_host[stream])
+            else:
+                src = ds.strong_row(rng.integers(0, ds.n_variants, size=N), stream) if self._is_strong(k) else stream
+                ops.check_token_rows(src, ds.row_len_host)
+                rows.append(src)
+                self.draws[k] = (src, ds.row_len_host[src[:nb * B]].reshape(nb, B).max(axis=1).astype(np.int64))
+        return np.stack(rows), where, N
+
+    def __iter__(self):
+        ds, B = self.dataset, self.batch_size
+        table, where, N = self._epoch_table()
+        dev = _h2d(torch.from_numpy(table), ds.device)                                     # the epoch's one copy, sliced per step
+        lengths = {k: v[1].tolist() for k, v in self.draws.items()}
+        for t in range(len(self)):
+            s = t * B
+            yield {k: (_view(ds, dev[where[k], s:s + B], lengths[k][t]) if k in lengths else dev[where[k], s:s + B]) for k in self.keys}
+
+
+class TokenEvalLoader:
+    """The dataset in order, last partial batch kept: {'x_lb': TokenBatch, 'y_lb'}, every batch right-padded to its own longest row -- the
+    reference's evaluation collator.  The host knows the lengths: no synchronisation and no host-to-device copy."""
+
+    def __init__(self, dataset, batch_size):
+        if dataset.targets is None:
+            raise ValueError("the evaluation loader needs a labelled dataset")
+        self.dataset, self.batch_size = dataset, int(batch_size)
+        self._rows = torch.arange(len(dataset), dtype=torch.int64, device=dataset.device)          # made on the device: nothing to copy
+
+    def __len__(self):
+        return -(-len(self.dataset) // self.batch_size)
+
+    def batch_lengths(self):
+        ds, n = self.dataset, len(self.dataset)
+        return [int(ds.row_len_host[s:min(s + self.batch_size, n)].max()) for s in range(0, n, self.batch_size)]
+
+    def __iter__(self):
+        ds, n = self.dataset, len(self.dataset)
+        for s, L in zip(range(0, n, self.batch_size), self.batch_lengths()):
+            e = min(s + self.batch_size, n)
+            yield {"x_lb": _view(ds, self._rows[s:e], L), "y_lb": ds.targets[s:e]}
+
+
+# ---- the tokenizer (needed only when a dataset holds strings) ----------------------------------------------------------------------------
+def load_tokenizer(directory, tried=()):
+    """``BertTokenizerFast.from_pretrained(directory, local_files_only=True)``: the vocabulary of a directory on disk, never the network."""
+    tried = list(tried) or [directory]
+    if not (os.path.isdir(directory) and any(os.path.isfile(os.path.join(directory, f)) for f in TOKENIZER_FILES)):
+        raise RuntimeError("device_tokens: %s holds no tokenizer files (%s); tried: %s" % (directory, " / ".join(TOKENIZER_FILES), ", ".join(map(str, tried))))
+    try:
+        from transformers import BertTokenizerFast
+    except ImportError as e:
+        raise RuntimeError("device_tokens: the datasets hold strings and transformers is not importable (%s): install it, or pass "
+                           "already-tokenised integer arrays; tokenizer directory tried: %s" % (e, ", ".join(map(str, tried))))
+    return BertTokenizerFast.from_pretrained(directory, local_files_only=True)
+
+
+def resolve_tokenizer(args):
+    """The tokenizer of the net's snapshot directory as nets/pretrained.find_snapshot resolves it: ``pretrain_path``, else the hub cache."""
+    from ..nets.pretrained import find_snapshot
+    net = str(getattr(args, "net", "") or "")
+    snap, tried = find_snapshot(HUB_NAMES.get(net), getattr(args, "pretrain_path", None))
+    if snap is None:
+        raise RuntimeError("device_tokens: the datasets hold strings and no snapshot directory with a tokenizer was found for net %r (tried: %s): "
+                           "set pretrain_path to a directory holding config.json, the weights and vocab.txt, or pass already-tokenised integer "
+                           "arrays" % (net, ", ".join(map(str, tried)) or "nothing to try"))
+    return load_tokenizer(snap, tried)
+
+
+def make_tokenize(tokenizer, max_length):
+    """The collator's call (nlp_collactor.py:51): str -> list of ids, truncated to ``max_length`` with [SEP] kept last, not padded."""
+    return lambda text: tokenizer(text, max_length=max_length, truncation=True, padding=False)["input_ids"]
+
+
+# ---- the option's wiring (core/algorithmbase.py) -----------------------------------------------------------------------------------------
+def _is_token_net(net):
+    net = str(net or "").lower()
+    return "bert" in net and "hubert" not in net
+
+
+def refuse_unsupported(args):
+    """The configurations the token loaders do not cover, each with its reason, decided from the yaml keys before any array is moved."""
+    for other, what in (("device_data", "images"), ("device_audio", "waveforms")):
+        if bool(getattr(args, other, False)):
+            raise ValueError("device_tokens and %s are two input pipelines (token batches / %s): set one of them" % (other, what))
+    net = getattr(args, "net", None)
+    if net and not _is_token_net(net):
+        raise NotImplementedError("device_tokens covers the usb_nlp token pipelines only (ClassificationBert backbones): net %r does not take "
+                                  "token batches" % (net,))
+    sampler = getattr(args, "train_sampler", "RandomSampler")
+    if sampler != "RandomSampler":
+        raise NotImplementedError("device_tokens: train_sampler %r is not supported (only 'RandomSampler', the reference's DistributedSampler "
+                                  "index stream, is restated on the device path)" % (sampler,))
+    view_length(args)
+
+
+def view_length(args):
+    ml = getattr(args, "max_length", None)
+    if ml is None or int(ml) <= 0:
+        raise ValueError("device_tokens needs args.max_length (the length the tokenizer truncates every sentence to), got %r" % (ml,))
+    return int(ml)
+
+
+def refuse_unsupported_model(model, dataset_dict=None):
+    """Decided from the model once it exists, before anything is launched: a backbone that takes no token batches, ``max_length`` beyond its
+    position table, a stored id beyond its vocabulary (the embedding kernel indexes the table with the ids: a bad id must never reach it)."""
+    if not getattr(model, "takes_tokens", False):
+        raise NotImplementedError("device_tokens covers the usb_nlp token pipelines only: this backbone (%s) does not take token batches"
+                                  % type(model).__name__)
+    for name, ds in (dataset_dict or {}).items():
+        if not isinstance(ds, DeviceTokenDataset):
+            continue
+        longest = int(ds.row_len_host.max()) if ds.max_length is None else ds.max_length
+        if longest > model.cfg.max_pos:
+            raise ValueError("device_tokens: max_length = %d of dataset %r exceeds the model's %d positions (max_pos)" % (longest, name, model.cfg.max_pos))
+        if ds.max_id_host >= model.cfg.vocab:
+            raise ValueError("device_tokens: dataset %r holds token id %d, outside the model's vocabulary of %d (the tokenizer and the "
+                             "checkpoint do not belong together)" % (name, ds.max_id_host, model.cfg.vocab))
+
+
+def _holds_strings(dset):
+    if dset is None or isinstance(dset, DeviceTokenDataset):
+        return False
+    data = list(dset["data"] if isinstance(dset, dict) else dset.data)
+    for var in ((dset.get("data_s") if isinstance(dset, dict) else getattr(dset, "data_s", None)) or ()):
+        data += list(var)
+    return _triples(data) is not None or any(_is_text(x) for x in data)
+
+
+def build_token_datasets(args, dataset_dict, device):
+    """dataset_dict values (reference-style objects, plain dicts or None) -> DeviceTokenDataset / None, same keys.  The tokenizer is looked
+    for only when a set holds strings; with already-tokenised rows transformers is never imported."""
+    refuse_unsupported(args)
+    max_length = view_length(args)
+    tokenize = make_tokenize(resolve_tokenizer(args), max_length) if any(_holds_strings(v) for v in dataset_dict.values()) else None
+    return {k: (None if v is None else DeviceTokenDataset.from_reference(v, device, tokenize, max_length)) for k, v in dataset_dict.items()}
+
+
+def build_token_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank):
+    """The loader_dict of AlgorithmBase.set_data_loader from resident datasets: train_lb (batch_size), train_ulb (batch_size * uratio),
+    eval / test (eval_batch_size).  ``step_keys``: the parameter names of the algorithm's train_step -- a view it does not take is not made."""
+    strong = "x_ulb_s" in step_keys
+    for name in ("train_lb", "train_ulb"):
+        if dataset_dict.get(name) is None:
+            raise ValueError("device_tokens: dataset_dict[%r] is missing or None; the train loaders need a labelled and an unlabelled set (every "
+                             "train_step of this project takes x_lb and x_ulb_w)" % name)
+    if strong and dataset_dict["train_ulb"].n_variants == 0:
+        raise ValueError("device_tokens: this algorithm's train_step takes x_ulb_s but the unlabelled set has no data_s; " + DATA_S_HELP)
+    seed = int(getattr(args, "seed", 0) or 0)
+    per_epoch = num_train_iter // max(1, epochs)
+    ld = {}
+    for name, bs, keys in (("train_lb", args.batch_size, ("idx_lb", "x_lb", "y_lb")),
+                           ("train_ulb", args.batch_size * args.uratio, ("idx_ulb", "x_ulb_w", "x_ulb_s"))):
+        ds = dataset_dict[name]
+        sampler = EpochSampler(len(ds), per_epoch * bs * num_replicas, num_replicas, rank)     # one seed (the epoch) for both, as the reference
+        ld[name] = TokenTrainLoader(ds, bs, sampler, strong=strong, keys=keys, seed=(seed, rank, ROLES[name]))
+    for name in ("eval", "test"):
+        if dataset_dict.get(name) is not None:
+            ld[name] = TokenEvalLoader(dataset_dict[name], args.eval_batch_size)
+    return ld

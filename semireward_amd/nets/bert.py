@@ -97,6 +97,18 @@ class TokenBatch:
             ops.mask_lengths(am.to(device=device, dtype=torch.int64).contiguous(), kl, S, L)
         return cls(ids, kl)
 
+    def to(self, device, non_blocking=False):
+        """What ``process_batch`` asks of every batch value: a batch already on ``device`` (the device token loaders') is returned as it is."""
+        if self.ids.device == torch.device(device):
+            return self
+        mv = lambda t: None if t is None else t.to(device, non_blocking=non_blocking)     # noqa: E731
+        return TokenBatch(mv(self.ids), mv(self.key_len), mv(self.seq_len))
+
+    def as_dict(self):
+        """The collator's {'input_ids', 'attention_mask'} (int64, on the batch's device): what ``from_dict`` would turn back into this batch."""
+        mask = (torch.arange(self.L, device=self.ids.device)[None, :] < self.key_len[:, None]).to(torch.int64)
+        return {"input_ids": self.ids, "attention_mask": mask}
+
     @classmethod
     def cat(cls, batches):
         """One batch out of several (x_lb, x_ulb_w, x_ulb_s of one step; the reference forwards them in separate model calls under

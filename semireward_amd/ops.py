@@ -1471,3 +1471,35 @@ def wave_view(store, row_off, row_len, src_row, crop_off, S, normalize, host=Non
     _call("srhip_wave_view", _p(store), _p(row_off), _p(row_len), int(row_len.shape[0]), _p(src_row), _p(crop_off), B, S, 1 if normalize else 0,
           _p(out), ldo, _s())
     return out if ldo == S else out[:, :S]
+
+
+def check_token_rows(src_row, row_len):
+    """The host-side argument check of ``token_view``: numpy ``src_row`` (where a loader produces it) against the numpy ``row_len`` of the
+    store.  The kernel turns such a row into an all-pad row; here it is an error."""
+    import numpy as np
+    src_row = np.asarray(src_row)
+    if src_row.ndim != 1 or src_row.dtype.kind not in "iu":
+        raise ValueError("token_view: src_row must be a 1-D integer array, got %s %s" % (src_row.dtype, src_row.shape))
+    if src_row.size and (src_row.min() < 0 or src_row.max() >= len(row_len)):
+        raise IndexError("token_view: src_row outside the store's %d rows" % len(row_len))
+
+
+def token_view(store, row_off, row_len, src_row, L, pad_id=0, host=None):
+    """One view of a batch from the flat int32 token store (srhip.h: srhip_token_view): row b holds the first L tokens of store row
+    ``src_row[b]``, right-padded with ``pad_id``.  store int32, row_off int64, row_len int32, src_row int64 [B], all on the device ->
+    (ids int64 [B, L] contiguous, key_len int32 [B]).  ``host``: (src_row, row_len) as numpy arrays, checked before the launch
+    (check_token_rows)."""
+    if store.dtype != torch.int32 or row_off.dtype != torch.int64 or row_len.dtype != torch.int32:
+        raise ValueError("token_view: the store is int32 with int64 row_off and int32 row_len, got %s / %s / %s" % (store.dtype, row_off.dtype, row_len.dtype))
+    if src_row.dtype != torch.int64 or src_row.dim() != 1:
+        raise ValueError("token_view: src_row is int64 [B], got %s %s" % (src_row.dtype, tuple(src_row.shape)))
+    if row_off.shape != row_len.shape or row_off.dim() != 1:
+        raise ValueError("token_view: row_off and row_len hold one entry per row")
+    if host is not None:
+        check_token_rows(*host)
+    B, L = int(src_row.shape[0]), int(L)
+    ids = torch.empty(B, L, dtype=torch.int64, device=store.device)
+    key_len = torch.empty(B, dtype=torch.int32, device=store.device)
+    _call("srhip_token_view", _p(store), _p(row_off), _p(row_len), int(row_len.shape[0]), _p(src_row), B, L, int(pad_id), _p(ids), L, _p(key_len),
+          _s())
+    return ids, key_len
