@@ -4,6 +4,7 @@
 class-dependent blobs (no network for CIFAR); the point is the plumbing: dataset arrays, per-step views, train loop, evaluate().
 
     python examples/train_synthetic_cifar.py --steps 60
+    python examples/train_synthetic_cifar.py --steps 60 --monitor-pseudo-labels     # + the pseudo-label monitor's keys in every log line
 """
 import argparse
 import os
@@ -36,6 +37,8 @@ def main():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--classes", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--monitor-pseudo-labels", action="store_true",
+                    help="monitor_pseudo_labels: True with the synthetic unlabelled set's labels (configs/README.md)")
     a = ap.parse_args()
     dev = "cuda:0"
     C, B = a.classes, a.batch
@@ -44,9 +47,11 @@ def main():
         lr=5e-4, weight_decay=5e-4, layer_decay=0.5, num_warmup_iter=5, optim="AdamW", T=0.5, p_cutoff=0.95, hard_label=True, thresh_warmup=True,
         ulb_dest_len=2048, N_k=10, start_timing=20, feature_dim=384, sr_lr=5e-4, sr_ema=False, sr_ema_m=0.99, gpu=0, rank=0, world_size=1,
         distributed=False)
-    alg = get_algorithm(args, vit.vit_small_patch2_32)
     x_lb, y_lb = synth_dataset(40 * C // 10, C, 1)                 # "40 labels"-style split
-    x_ulb, _ = synth_dataset(2048, C, 2)
+    x_ulb, y_ulb = synth_dataset(2048, C, 2)
+    if a.monitor_pseudo_labels:                                    # the labels the unlabelled set was carved from: the monitor's only source
+        args.monitor_pseudo_labels, args.ulb_targets = True, y_ulb
+    alg = get_algorithm(args, vit.vit_small_patch2_32)
     x_te, y_te = synth_dataset(512, C, 3)
     lb, ulb = torch.from_numpy(x_lb).to(dev), torch.from_numpy(x_ulb).to(dev)     # the dataset lives in HBM as uint8
     aug = GpuAugment(32, 4, MEAN, STD, n_ops=3, device=dev, seed=0)               # crop_ratio 0.875 -> padding 4
@@ -72,8 +77,12 @@ def main():
         alg.out_dict, alg.log_dict = alg.train_step(**alg.process_batch(**next(it)))
         alg.call_hook("after_train_step")
         if step % 10 == 0 or step == a.steps - 1:
-            print("it %3d  sup %.3f  unsup %.3f  util %.2f" % (step, float(alg.log_dict["train/sup_loss"]), float(alg.log_dict["train/unsup_loss"]),
-                                                              float(alg.log_dict["train/util_ratio"])), flush=True)
+            line = "it %3d  sup %.3f  unsup %.3f  util %.2f" % (step, float(alg.log_dict["train/sup_loss"]), float(alg.log_dict["train/unsup_loss"]),
+                                                               float(alg.log_dict["train/util_ratio"]))
+            if a.monitor_pseudo_labels:                            # the steps since the previous line, from one copy of the device counters
+                line += "".join("  %s %.3f" % (k[len("train/"):], float(v)) for k, v in alg.log_dict.items()
+                                if k.startswith("train/") and k[len("train/"):] in alg.pl_monitor.log_keys)
+            print(line, flush=True)
     ev = alg.evaluate(loader=list(eval_loader()))
     print("eval:", {k: round(float(v), 4) for k, v in ev.items()})
     return ev

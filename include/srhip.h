@@ -481,6 +481,46 @@ int srhip_consistency_l1(const float* logits, long long ld, const float* targets
 int srhip_eval_accumulate(const float* logits, long long ld, const long long* y, int* confusion, void* state, long long* pred_out,
                           long long row_offset, int B, int C, void* stream);
 
+/* Pseudo-label quality monitor (``monitor_pseudo_labels: True``, pl_monitor.hip): what ONE training step's masks, pseudo labels, rewards and
+ * reward filter say about the true labels of the unlabelled rows, added into device-resident counters by one launch.  K = P - 1 is the step's
+ * number of data_generator passes (srflexmatch.py:72-104); the step keeps the loss of pass K.
+ *   pseudo      int64 [P * nu]   argmax of the weak rows of every pass (pass p at p * nu)
+ *   mask0       fp32 [nu]        the confidence mask of pass 0 (what util_ratio describes)
+ *   mask_kept   fp32 [nu]        the confidence mask of pass K (== mask0 when K == 0); the masks of the passes between are not read
+ *   mask2       fp32 [K * nu]    the reward filter of the data_generator passes; NULL when K == 0
+ *   reward      fp32 [K * nu]    the rewarder's scores of the data_generator passes; NULL when K == 0
+ *   idx_ulb     int64 [nu]       the rows' positions in the unlabelled set
+ *   ulb_targets int64 [n_ulb]    the true labels of the unlabelled set, -1 = unknown
+ * Weak row j, y = ulb_targets[idx_ulb[j]]:
+ *   idx_ulb[j] outside [0, n_ulb) or y >= C: the row reaches no counter and bit 5 of the word srhip_label_error reads is set; nothing is read
+ *   out of bounds.  y < 0: rows_unknown += 1 and the row reaches nothing else.  Otherwise
+ *   kept pass   pl = pseudo[K * nu + j]; w = mask_kept[j] (K == 0) or mask_kept[j] * mask2[(K - 1) * nu + j], ONE fp32 product as the
+ *               consistency loss takes it.  rows += 1, rows_correct += (pl == y), sel += (w > 0), sel_correct += (w > 0 && pl == y),
+ *               sum_w += w, sum_w_correct += w where pl == y, and for w > 0 and 0 <= pl < C: sel_by_class[pl] += 1,
+ *               sel_correct_by_class[pl] += (pl == y)
+ *   pass 0      conf_sel += (mask0[j] > 0), conf_sel_correct += (mask0[j] > 0 && pseudo[j] == y)
+ *   every data_generator pass g = 0 .. K - 1:  r = reward[g * nu + j], ok = (pseudo[(g + 1) * nu + j] == y):
+ *               gen_rows += 1, gen_correct += ok, m2 += (mask2[g * nu + j] > 0), m2_correct += (mask2 > 0 && ok);
+ *               0 <= r <= 1: hist[ok][min((int)(r * 32.0f), 31)] += 1 (r * 32 is exact in fp32) and sum_r[ok] += r;
+ *               any other r (NaN included): reward_bad += 1, neither binned nor summed
+ * and steps += 1 per launch.
+ * State, the caller's, zeroed by the caller, both blocks 8-byte aligned:
+ *   istate int64 [16 + 2 * C + 64]:
+ *     [0] steps  [1] rows  [2] rows_correct  [3] sel  [4] sel_correct  [5] conf_sel  [6] conf_sel_correct  [7] rows_unknown  [8] gen_rows
+ *     [9] gen_correct  [10] reward_bad  [11] m2  [12] m2_correct  [13 .. 15] reserved (never written)
+ *     [16, 16 + C) sel_by_class   [16 + C, 16 + 2 C) sel_correct_by_class
+ *     [16 + 2 C, + 32) hist[0] (wrong pseudo labels)   [16 + 2 C + 32, + 32) hist[1] (right pseudo labels)
+ *   fstate double [4]: sum_w, sum_w_correct, sum_r[0] (wrong), sum_r[1] (right)
+ * One workgroup; the rows' true labels staged in LDS once (rows j < 2048; gathered at every use beyond); integer counters in registers /
+ * LDS (per-class counters in LDS for C <= 2048, global 64-bit integer atomics beyond); the fp64
+ * sums are added per thread in element order, then over a fixed tree: no float atomics, a launch on equal inputs gives equal bits, whether
+ * reward / mask2 are 16-byte aligned (16-byte loads, the end peeled) or not.  Launches that share a state must be ordered (one stream).
+ * SR_EINVAL before any launch: a null pointer other than mask2 / reward, P <= 0, nu <= 0, C <= 0, n_ulb <= 0, P > 1 with a NULL mask2 or
+ * reward, P * nu >= 2^31, C > 2^28, a state / int64 pointer that is not 8-byte aligned. */
+int srhip_pl_monitor(const long long* pseudo, const float* mask0, const float* mask_kept, const float* mask2, const float* reward,
+                     const long long* idx_ulb, const long long* ulb_targets, long long n_ulb, int P, int nu, int C, long long* istate,
+                     double* fstate, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Rewarder / Generator (K10, K14, K15).  params: flat fp32 block in named_parameters() order.
  * Rewarder.forward (semilearn/algorithms/semireward/semireward.py:52-72) for G independent groups of B rows
@@ -519,7 +559,7 @@ int srhip_sr_target(const long long* gen, const long long* ref, float* target, i
  * gradient scatter is skipped), set a bit in a device word and the host raises when it reads it here (SYNCHRONISES the stream):
  * bit 0 embedding lookup, bit 1 embedding-gradient scatter, bit 2 generator output NaN / not representable as int64, bit 3 a label outside
  * [0, num_classes) in srhip_sr_target (F.one_hot; num_classes <= 0 disables that check), bit 4 an evaluation label outside [-1, C) in
- * srhip_eval_accumulate. */
+ * srhip_eval_accumulate, bit 5 an idx_ulb outside [0, n_ulb) or a true label >= C in srhip_pl_monitor. */
 int srhip_label_error(int* bits_out, int reset, void* stream);
 /* torch.optim.Adam step on a flat block (srflexmatch.py:54, :192-193). */
 /* "_dyn" entry points: the scalars that change from step to step -- the scheduler's lr factor and Adam's bias corrections (param_update.py:33-40,

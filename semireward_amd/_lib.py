@@ -96,6 +96,7 @@ SIGNATURES = {
     "srhip_consistency_mse": (I, [P, c_longlong, P, c_longlong, P, P, F, I, P, P, P, c_longlong, I, I, P]),
     "srhip_consistency_l1": (I, [P, c_longlong, P, c_longlong, P, P, F, I, P, P, P, c_longlong, I, I, P]),
     "srhip_eval_accumulate": (I, [P, c_longlong, P, P, P, P, c_longlong, I, I, P]),
+    "srhip_pl_monitor": (I, [P, P, P, P, P, P, P, c_longlong, I, I, I, P, P, P]),
     "srhip_rewarder_param_count": (L, [I, I]),
     "srhip_rewarder_ws_floats": (L, [I, I]),
     "srhip_generator_param_count": (L, [I]),

@@ -921,6 +921,8 @@ class SRConsistencyBase(AlgorithmBase):
         out_dict = self.process_out_dict(loss=total_loss, feat=feat_dict)
         log_dict = self.process_log_dict(sup_loss=DeferredScalar(sup_loss), unsup_loss=DeferredScalar(unsup_loss),
                                          total_loss=DeferredScalar(total_loss), util_ratio=DeferredScalar(lambda m=masks[0]: m.mean()))
+        if getattr(self, "pl_monitor", None) is not None:      # monitor_pseudo_labels: one launch into device counters, eight lazy log values
+            self.process_log_dict(log_dict, **self.monitor_step(K, masks, mi, reward, mask2, idx_ulb))
         return out_dict, log_dict
 
     def _sr_save(self, d):

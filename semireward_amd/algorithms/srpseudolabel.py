@@ -136,6 +136,8 @@ class SRPseudoLabel(SRConsistencyBase):
         out_dict = self.process_out_dict(loss=total_loss, feat={"x_lb": fx, "x_ulb_w": fu0})
         log_dict = self.process_log_dict(sup_loss=DeferredScalar(sup_loss), unsup_loss=DeferredScalar(unsup_loss),
                                          total_loss=DeferredScalar(total_loss), util_ratio=DeferredScalar(masks[0].mean()))
+        if getattr(self, "pl_monitor", None) is not None:      # monitor_pseudo_labels: one launch into device counters, eight lazy log values
+            self.process_log_dict(log_dict, **self.monitor_step(K, masks, mi, reward, mask2))
         return out_dict, log_dict
 
     @staticmethod

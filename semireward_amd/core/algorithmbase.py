@@ -107,7 +107,14 @@ class AlgorithmBase:
         self.device_tokens = bool(g("device_tokens", False)) # token rows resident in HBM, loaders of data/device_tokens.py (usb_nlp)
         self.device_eval = bool(g("device_eval", False))     # evaluate() accumulates loss and confusion matrix on the device (csrc/eval.hip)
         self.run_hooks = bool(g("run_hooks", False))         # the reference's EvaluationHook / CheckpointHook / LoggingHook join the hook list
+        monitor = bool(g("monitor_pseudo_labels", False))    # per-step pseudo-label quality counters on the device (core/pl_monitor.py)
+        if monitor:                                          # refused from the yaml keys, before a dataset is looked at
+            from .pl_monitor import PlMonitor
+            PlMonitor.check_targets(g("ulb_targets"))
         self.dataset_dict = self.set_dataset()
+        if monitor:                                          # off: no attribute, no allocation, no launch, the same log keys
+            self.pl_monitor = PlMonitor(args.ulb_targets, self.num_classes, self.device, g("ulb_dest_len") or None)
+            self._monitor_idx_ulb = None
         self.loader_dict = self.set_data_loader()
         self.model = self.set_model()
         if self.device_data:
@@ -278,6 +285,10 @@ class AlgorithmBase:
             else:
                 var = var.to(self.device, non_blocking=True)
             out[arg] = var
+        if getattr(self, "pl_monitor", None) is not None:
+            # the monitor needs the batch's idx_ulb also where train_step does not take it: kept aside, on the device, before the filter drops it
+            idx = out.get("idx_ulb", kwargs.get("idx_ulb"))
+            self._monitor_idx_ulb = None if idx is None else idx.to(self.device, non_blocking=True)
         return out
 
     def process_out_dict(self, out_dict=None, **kwargs):
@@ -290,6 +301,17 @@ class AlgorithmBase:
         for k, v in kwargs.items():
             log_dict[prefix + "/" + k] = v
         return log_dict
+
+    def monitor_step(self, K, masks, pseudo, reward, mask2, idx_ulb=None):
+        """``monitor_pseudo_labels: True``: the step's ONE monitor launch, and the eight lazy log values that describe the steps since the
+        previous read.  idx_ulb: the train_step argument where the algorithm takes it, else the one process_batch kept aside."""
+        idx = idx_ulb if idx_ulb is not None else self._monitor_idx_ulb
+        self._monitor_idx_ulb = None
+        if idx is None:
+            raise ValueError("monitor_pseudo_labels needs idx_ulb in every unlabelled batch (the rows' positions in the unlabelled set): "
+                             "this batch has none")
+        self.pl_monitor.accumulate(K, masks, pseudo, reward, mask2, idx.long().contiguous())
+        return self.pl_monitor.log_values(self.it)
 
     def compute_prob(self, logits):
         return torch.softmax(logits, dim=-1)     # API parity only; the hot path fuses softmax into srhip_row_max
@@ -502,6 +524,8 @@ class AlgorithmBase:
             self.optimizer.sched_step = int(sch["last_epoch"])
         if "engine_rng" in ck and hasattr(self.model, "_rng_calls"):
             self.model.seed, self.model._rng_calls = int(ck["engine_rng"]["seed"]), int(ck["engine_rng"]["draws"])
+        if getattr(self, "pl_monitor", None) is not None:         # the monitor's window is not checkpointed: a resumed run starts an empty one
+            self.pl_monitor.restart()
         return ck
 
     # ---- hooks (algorithmbase.py:548-599) ---------------------------------------------------------------------

@@ -85,7 +85,8 @@ class StepGraph:
 
     With ``share_pass_prefixes`` on, every step runs eagerly and none is captured: the pass-prefix trees of the step's inference launch trains
     follow that step's DropPath draws, so their launch shapes (node counts per block, forks) change from step to step and a captured graph
-    would replay the wrong ones."""
+    would replay the wrong ones.  With ``monitor_pseudo_labels`` on, every step runs eagerly too: the monitor's log values are bound to the
+    step that made them and its window is read and zeroed between steps, outside any graph."""
 
     MAX_GRAPHS = 8           # captured variants kept (least recently used one dropped beyond that)
     COUNTERS = (("optimizer", "step_count"), ("optimizer", "sched_step"), ("model", "_rng_calls"), ("rewarder_optimizer", "steps"))
@@ -159,7 +160,7 @@ class StepGraph:
         n = self.seen.get(key, 0)
         self.seen[key] = n + 1
         if n < self.warm or getattr(alg, "_tuners", None) or getattr(alg, "_untuned", None) or alg.trace is not None or split is None or \
-                getattr(alg, "share_pass_prefixes", False):
+                getattr(alg, "share_pass_prefixes", False) or getattr(alg, "pl_monitor", None) is not None:
             self.eager_steps += 1
             return self._eager(batch)
         # ---- capture this step (nothing executes during capture), then replay it once: that IS this step

@@ -923,6 +923,30 @@ def eval_accumulate(logits, y, confusion, state, pred_out=None, row_offset=0):
     _call("srhip_eval_accumulate", z, ld, _p(y), _p(confusion), _p(state), _p(pred_out), row_offset, B, C, _s())
 
 
+# ---- pseudo-label quality monitor -----------------------------------------------------------------
+PL_HEADER_WORDS, PL_BINS, PL_SUMS = 16, 32, 4          # srhip_pl_monitor's state layout (include/srhip.h)
+
+
+def pl_monitor_words(C):
+    """int64 words of srhip_pl_monitor's integer state: the header, 2 * C per-class counters, 2 * 32 histogram bins."""
+    return PL_HEADER_WORDS + 2 * C + 2 * PL_BINS
+
+
+def pl_monitor(pseudo, mask0, mask_kept, mask2, reward, idx_ulb, ulb_targets, P, nu, C, istate, fstate):
+    """One training step into the monitor's device counters (srhip_pl_monitor): pseudo int64 [P * nu], mask0 / mask_kept fp32 [nu] (the
+    confidence masks of pass 0 and of the kept pass P - 1), mask2 / reward fp32 [(P - 1) * nu] or None when P == 1, idx_ulb int64 [nu],
+    ulb_targets int64 [n_ulb]; istate int64 [pl_monitor_words(C)] and fstate float64 [4] are the caller's and start at zero."""
+    if _CHECK_ARGS:
+        assert pseudo.dtype == torch.int64 and pseudo.numel() >= P * nu and idx_ulb.dtype == torch.int64 and idx_ulb.numel() == nu
+        assert mask0.dtype == torch.float32 and mask0.numel() >= nu and mask_kept.dtype == torch.float32 and mask_kept.numel() >= nu
+        assert P == 1 or (mask2.dtype == torch.float32 and mask2.numel() >= (P - 1) * nu and reward.dtype == torch.float32 and
+                          reward.numel() >= (P - 1) * nu)
+        assert ulb_targets.dtype == torch.int64 and istate.dtype == torch.int64 and istate.numel() == pl_monitor_words(C)
+        assert fstate.dtype == torch.float64 and fstate.numel() == PL_SUMS
+    _call("srhip_pl_monitor", _p(pseudo), _p(mask0), _p(mask_kept), _p(mask2), _p(reward), _p(idx_ulb), _p(ulb_targets),
+          int(ulb_targets.numel()), P, nu, C, _p(istate), _p(fstate), _s())
+
+
 # ---- rewarder / generator ---------------------------------------------------------------------
 def rewarder_param_count(F, L):
     return int(_lib.lib().srhip_rewarder_param_count(F, L))
@@ -979,7 +1003,9 @@ _LABEL_ERR = ("a label outside [0, label_dim) reached the rewarder's nn.Embeddin
               "a label outside [0, label_dim) reached the embedding gradient (semireward.py:57)",
               "the generator output is NaN or not representable as int64 (srflexmatch.py:158-159)",
               "a label outside [0, num_classes) reached F.one_hot of the SR target (srflexmatch.py:180-181, :195-196)",
-              "an evaluation label outside [-1, num_classes) reached F.cross_entropy (algorithmbase.py:407)")
+              "an evaluation label outside [-1, num_classes) reached F.cross_entropy (algorithmbase.py:407)",
+              "an idx_ulb entry outside [0, len(ulb_targets)) or a true label >= num_classes reached the pseudo-label monitor "
+              "(monitor_pseudo_labels)")
 
 
 def check_label_errors(reset=True):
