@@ -434,7 +434,7 @@ int srhip_softmatch_mask(const float* maxp_all, int n_all, const float* max_prob
 int srhip_freematch_entropy(const float* logits, const float* mask, const float* p_model, const float* label_hist, float grad_scale,
                             float* loss_out, float* dlogits, float* ws, int B, int C, int accumulate, void* stream);
 /* mask2 = (reward >= reward.mean()) per independent group of B rows (srflexmatch.py:100-101) (K11).
- * mean_in (optional, [groups]) overrides the local mean: data-parallel global-threshold extension. */
+ * mean_in (optional, [groups]) overrides the local mean: data-parallel global-threshold extension.  groups * B < 2^31. */
 int srhip_reward_mask2(const float* reward, float* mask2, float* mean_out, const float* mean_in, int groups, int B,
                        void* stream);
 /* ce_loss / consistency_loss forward + analytic backward (semilearn/core/criterions/cross_entropy.py:11-31,
@@ -521,6 +521,51 @@ int srhip_pl_monitor(const long long* pseudo, const float* mask0, const float* m
                      const long long* idx_ulb, const long long* ulb_targets, long long n_ulb, int P, int nu, int C, long long* istate,
                      double* fstate, void* stream);
 
+/* Scoring a whole unlabelled set without touching training state (AlgorithmBase.score_unlabeled, score_rows.hip).
+ *
+ * srhip_score_rows: one batch of logits, fp32 [B, C] with row stride ld (elements, >= C; the base need not be 16-byte aligned), and the
+ * threshold rule's state, READ ONLY.  Per row b, all outputs dense [B]:
+ *   label int64, conf fp32   argmax and max of softmax(z_b): the bits srhip_row_max gives (the row-softmax body is shared, csrc/row_softmax.h;
+ *                            the first column wins a tie; a row of NaNs gives 0x7fffffff / -inf as there).  SOFT with the three da_*
+ *                            pointers and *da_inited != 0: taken from the aligned, renormalised probabilities
+ *                            q_c = p_c (da_p_target[c] + 1e-6) / (da_p_model[c] + 1e-6), q / sum(q), the bits srhip_distalign gives; so are margin
+ *                            and entropy.  *da_inited == 0: unaligned.  da_p_model / da_p_target are not written.
+ *   margin fp32              conf - the second largest probability: 0 for a tie at the top, conf for C == 1
+ *   entropy fp32             -sum_c p_c ln p_c with 0 ln 0 = 0
+ *   weight fp32              the rule's mask / weight from the state as it stands, no update, in the expression order of the hook kernels:
+ *     SRHIP_SCORE_FIXED  conf >= p_cutoff                                                   (masking.py:42-57, srhip_fixed_mask)
+ *     SRHIP_SCORE_FLEX   conf >= p_cutoff * (acc / (2 - acc)), acc = classwise_acc[label]   (srflexmatch/utils.py:50-56, srhip_flexmatch_mask)
+ *     SRHIP_SCORE_FREE   conf >= time_p[0] * (p_model[label] / max(0, max_c p_model[c]))    (freematch/utils.py:24-66, srhip_freematch_update)
+ *     SRHIP_SCORE_SOFT   exp(-(min(conf - mu, 0)^2 / ((2 var) / n_sigma^2))), (mu, var) = mu_var[0..1]   (srsoftmatch/utils.py:32-76)
+ *     a label outside [0, C) (the row of NaNs) gives weight 0 in FLEX and FREE.
+ * One wave per row, four rows per workgroup; rows of C <= 1024 live in registers, longer ones are re-read; 16-byte loads with head and tail
+ * peeled; no atomics: equal inputs give equal bits.
+ * SR_EINVAL before any launch: a NULL logits / output pointer, B outside 1 .. 65535, C < 1, ld < C, an unknown mode, a state pointer the mode
+ * needs that is NULL (FLEX classwise_acc; FREE time_p, p_model; SOFT mu_var, n_sigma >= 1; the da_* pointers all three or none), label not
+ * 8-byte aligned.
+ *
+ * srhip_score_commit: scatters one scored batch into device tables of length n.  Row b goes to entry j = idx[b], or row_offset + b when idx is
+ * NULL: t_label / t_conf / t_margin / t_entropy / t_weight / t_reward [j] = the batch's values, t_reward_keep[j] = (reward_keep[b] > 0) with
+ * reward_keep the fp32 mask srhip_reward_mask2 wrote for the row's reward group, t_selected[j] = (weight[b] > 0 && reward_keep[b] > 0),
+ * t_count[j] += 1 (integer atomic).  A j outside [0, n) is skipped and sets bit 6 of the word srhip_label_error reads.  idx must be unique
+ * within a launch; across launches of one stream the later one wins, and t_count > 1 shows the repeat.
+ * SR_EINVAL before any launch: a NULL pointer other than idx, B outside 1 .. 65535, n < 1, idx NULL with row_offset < 0, label / t_label /
+ * idx not 8-byte aligned. */
+#define SRHIP_SCORE_FIXED 0
+#define SRHIP_SCORE_FLEX 1
+#define SRHIP_SCORE_FREE 2
+#define SRHIP_SCORE_SOFT 3
+int srhip_score_rows(const float* logits, long long ld, int B, int C, int mode, float p_cutoff, const float* classwise_acc,
+                     const float* time_p, const float* p_model, const float* mu_var, int n_sigma, const float* da_p_model,
+                     const float* da_p_target, const int* da_inited, long long* label, float* conf, float* margin, float* entropy,
+                     float* weight, void* stream);
+int srhip_score_commit(const long long* label, const float* conf, const float* margin, const float* entropy, const float* weight,
+                       const float* reward, const float* reward_keep, const long long* idx, long long row_offset, int B, long long n,
+                       long long* t_label, float* t_conf, float* t_margin, float* t_entropy, float* t_weight, float* t_reward,
+                       unsigned char* t_reward_keep, unsigned char* t_selected, int* t_count, void* stream);
+/* srhip_reward_mask2 over `total` rows in groups of B, the last group holding the rows that are left (its own mean over those rows). */
+int srhip_reward_mask2_ragged(const float* reward, float* mask2, float* mean_out, int total, int B, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Rewarder / Generator (K10, K14, K15).  params: flat fp32 block in named_parameters() order.
  * Rewarder.forward (semilearn/algorithms/semireward/semireward.py:52-72) for G independent groups of B rows
@@ -559,7 +604,8 @@ int srhip_sr_target(const long long* gen, const long long* ref, float* target, i
  * gradient scatter is skipped), set a bit in a device word and the host raises when it reads it here (SYNCHRONISES the stream):
  * bit 0 embedding lookup, bit 1 embedding-gradient scatter, bit 2 generator output NaN / not representable as int64, bit 3 a label outside
  * [0, num_classes) in srhip_sr_target (F.one_hot; num_classes <= 0 disables that check), bit 4 an evaluation label outside [-1, C) in
- * srhip_eval_accumulate, bit 5 an idx_ulb outside [0, n_ulb) or a true label >= C in srhip_pl_monitor. */
+ * srhip_eval_accumulate, bit 5 an idx_ulb outside [0, n_ulb) or a true label >= C in srhip_pl_monitor, bit 6 a table index outside [0, n) in
+ * srhip_score_commit. */
 int srhip_label_error(int* bits_out, int reset, void* stream);
 /* torch.optim.Adam step on a flat block (srflexmatch.py:54, :192-193). */
 /* "_dyn" entry points: the scalars that change from step to step -- the scheduler's lr factor and Adam's bias corrections (param_update.py:33-40,

@@ -19,6 +19,7 @@ X3_EPI_F32, X3_EPI_GELU_F32, X3_EPI_RESID_F32 = range(3)     # srhip_gemm_nt_x3
 X3B_NT, X3B_NN = range(2)                                      # srhip_gemm_x3 layouts
 X3B_EPI_F32, X3B_EPI_ACC, X3B_EPI_DGELU, X3B_EPI_GELU_PRE = range(4)  # srhip_gemm_x3 epilogues
 REDUCE_NONE, REDUCE_MEAN, REDUCE_SUM = range(3)               # srhip_ce_hard / ce_soft / consistency_mse / consistency_l1
+SCORE_FIXED, SCORE_FLEX, SCORE_FREE, SCORE_SOFT = range(4)    # srhip_score_rows modes
 
 P, I, F, L, Dbl, U = c_void_p, c_int, c_float, c_long, c_double, c_uint
 SIGNATURES = {
@@ -97,6 +98,9 @@ SIGNATURES = {
     "srhip_consistency_l1": (I, [P, c_longlong, P, c_longlong, P, P, F, I, P, P, P, c_longlong, I, I, P]),
     "srhip_eval_accumulate": (I, [P, c_longlong, P, P, P, P, c_longlong, I, I, P]),
     "srhip_pl_monitor": (I, [P, P, P, P, P, P, P, c_longlong, I, I, I, P, P, P]),
+    "srhip_score_rows": (I, [P, c_longlong, I, I, I, F, P, P, P, P, I, P, P, P, P, P, P, P, P, P]),
+    "srhip_score_commit": (I, [P, P, P, P, P, P, P, P, c_longlong, I, c_longlong, P, P, P, P, P, P, P, P, P, P]),
+    "srhip_reward_mask2_ragged": (I, [P, P, P, I, I, P]),
     "srhip_rewarder_param_count": (L, [I, I]),
     "srhip_rewarder_ws_floats": (L, [I, I]),
     "srhip_generator_param_count": (L, [I]),

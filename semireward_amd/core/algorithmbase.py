@@ -486,6 +486,47 @@ class AlgorithmBase:
             out[eval_dest + "/logits"] = torch.cat(logits_all).cpu().numpy()
         return out
 
+    # ---- pseudo labels of the whole unlabelled set (core/pl_table.py) ------------------------------------------
+    def score_unlabeled(self, loader=None, use_ema_model=False, batch_size=None, reward_group=None):
+        """Score every row of an unlabelled loader with the model, the algorithm's threshold rule and the Rewarder AS THEY STAND, and return
+        the ``PseudoLabelTable`` (one entry per unlabelled sample: label, conf, margin, entropy, weight, reward, reward_keep, selected, count).
+
+        The backbone runs with ``training = False`` (no DropPath / dropout / SpecAugment / LayerDrop, running statistics for BatchNorm) on
+        ``self.model`` -- the thresholds were calibrated on it -- or on the EMA weights (``use_ema_model``).  Rewards come from
+        ``self.rewarder`` in groups of ``reward_group`` rows (default: the training step's ``batch_size * uratio``; the Rewarder's attention is
+        a softmax over its group, so only that size gives what training would see); a batch's last group holds the rows that are left.
+        A batch is evaluation style ({'x_lb'}) or training style ({'x_ulb_w'}, optional 'idx_ulb'); without ``idx_ulb`` the rows are numbered
+        in arrival order.  ``loader=None``: with device_data / device_audio / device_tokens, that mode's evaluation loader over
+        ``dataset_dict['train_ulb']`` (the unaugmented view in index order) at ``batch_size`` or ``eval_batch_size``.
+        Nothing is mutated: parameters, hook state, ``max_reward``, the Rewarder, the DropPath draw counter and ``it`` stay as they are;
+        step-timing state is invalidated as ``evaluate()`` does.  Under data parallel each rank scores what it is given; no collective."""
+        from .pl_table import score_loader, unlabelled_eval_loader
+        if getattr(self, "rewarder", None) is None or "MaskingHook" not in self.hooks_dict:
+            raise NotImplementedError("score_unlabeled needs a SemiReward algorithm (a MaskingHook and a rewarder)")
+        a = self.args
+        if loader is None:
+            if not (self.device_data or self.device_audio or self.device_tokens):
+                raise ValueError("score_unlabeled: pass loader= (an iterable of {'x_lb'} or {'x_ulb_w', 'idx_ulb'} batches); loader=None builds "
+                                 "one only with device_data, device_audio or device_tokens")
+            loader = unlabelled_eval_loader(self, int(batch_size or a.eval_batch_size))
+        n = int(getattr(a, "ulb_dest_len", 0) or 0)
+        if n <= 0:
+            raise ValueError("score_unlabeled needs args.ulb_dest_len (the number of unlabelled samples: the table's length)")
+        if reward_group is None:
+            reward_group = int(a.batch_size) * int(a.uratio)
+        if int(reward_group) < 1:
+            raise ValueError("score_unlabeled: reward_group must be >= 1, got %r" % (reward_group,))
+        self._invalidate_step_timing()
+        net = self.ema_model if use_ema_model else self.model
+        if net is not self.model:
+            net.refresh_operands()                    # bf16 operand copy of the EMA block, as evaluate()
+        was_training = getattr(net, "training", True)
+        net.training = False
+        try:
+            return score_loader(self, net, loader, n, int(reward_group))
+        finally:
+            net.training = was_training
+
     # ---- checkpoints (algorithmbase.py:459-547) ----------------------------------------------------------
     def get_save_dict(self):
         d = {"model": self.model.state_dict(), "ema_model": self.ema_model.state_dict(),

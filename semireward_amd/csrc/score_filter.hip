@@ -19,21 +19,12 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "row_softmax.h"
 #include "srhip.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-// wave-level (value, index) max with first-index tie break (torch.max / argmax semantics)
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, 64);
-    const int oi = __shfl_xor(i, o, 64);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-}
 
 // One wave per row.  in_is_probs = 0: logits -> softmax (fp32) ; 1: rows are already probabilities.
 __global__ __launch_bounds__(256) void row_max_kernel(const float* __restrict__ in, int in_is_probs, float* __restrict__ probs_out,
@@ -46,18 +37,13 @@ __global__ __launch_bounds__(256) void row_max_kernel(const float* __restrict__ 
   const float* r = rows_per_group > 0 ? in + (size_t)(row / rows_per_group) * group_stride + (size_t)(row % rows_per_group) * C
                                       : in + (size_t)row * C;
   float inv = 1.0f, mx = 0.f;
-  if (!in_is_probs) {
-    mx = -INFINITY;
-    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, r[c]);
-    mx = wave_max(mx);
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += expf(r[c] - mx);
-    inv = 1.0f / wave_sum(s);
-  }
+  // the row-softmax body of row_softmax.h (shared with srhip_score_rows, which must give the same bits)
+  if (!in_is_probs)
+    row_softmax_norm([&](auto&& g) { for (int c = lane; c < C; c += 64) g(c, r[c]); }, mx, inv);
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   for (int c = lane; c < C; c += 64) {
-    const float p = in_is_probs ? r[c] : expf(r[c] - mx) * inv;
+    const float p = in_is_probs ? r[c] : row_softmax_prob(r[c], mx, inv);
     if (probs_out) probs_out[(size_t)row * C + c] = p;
     if (p > bv) { bv = p; bi = c; }
   }
@@ -237,9 +223,11 @@ __global__ void fixed_mask_kernel(const float* __restrict__ max_probs, float p_c
 // mask2[g, i] = reward[g, i] >= mean_i(reward[g, :]);  one workgroup per independent group g.
 // Mean: fp32, fixed order.  B <= 64: left-to-right (== torch CPU for the reference batch of 8);
 // larger B: per-lane strided partials then a fixed shuffle tree (deterministic).
+// total: rows in all (srhip_reward_mask2_ragged: the last group holds the total - (groups - 1) * Bg rows that are left).
 __global__ __launch_bounds__(64) void reward_mask2_kernel(const float* __restrict__ reward, float* __restrict__ mask2,
-                                                         float* __restrict__ mean_out, const float* __restrict__ mean_in, int B) {
-  const float* r = reward + (size_t)blockIdx.x * B;
+                                                         float* __restrict__ mean_out, const float* __restrict__ mean_in, int Bg, int total) {
+  const float* r = reward + (size_t)blockIdx.x * Bg;
+  const int B = min(Bg, total - (int)blockIdx.x * Bg);
   const int lane = threadIdx.x;
   float s;
   if (mean_in) {                      // externally supplied threshold (data-parallel global mean extension)
@@ -253,7 +241,7 @@ __global__ __launch_bounds__(64) void reward_mask2_kernel(const float* __restric
     s = wave_sum(p);
   }
   const float mean = mean_in ? mean_in[blockIdx.x] : s / (float)B;
-  for (int i = lane; i < B; i += 64) mask2[(size_t)blockIdx.x * B + i] = r[i] >= mean ? 1.0f : 0.0f;
+  for (int i = lane; i < B; i += 64) mask2[(size_t)blockIdx.x * Bg + i] = r[i] >= mean ? 1.0f : 0.0f;
   if (mean_out && lane == 0) mean_out[blockIdx.x] = mean;
 }
 
@@ -563,7 +551,16 @@ extern "C" int srhip_fixed_mask(const float* max_probs, float p_cutoff, float* m
 extern "C" int srhip_reward_mask2(const float* reward, float* mask2, float* mean_out, const float* mean_in, int groups, int B,
                                   void* stream) {
   if (groups <= 0 || B <= 0) return SR_EINVAL;
-  SR_LAUNCH(reward_mask2_kernel, dim3(groups), dim3(64), 0, (hipStream_t)stream, reward, mask2, mean_out, mean_in, B);
+  if ((long long)groups * B > 0x7fffffffll) return SR_EINVAL;
+  SR_LAUNCH(reward_mask2_kernel, dim3(groups), dim3(64), 0, (hipStream_t)stream, reward, mask2, mean_out, mean_in, B, groups * B);
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+
+extern "C" int srhip_reward_mask2_ragged(const float* reward, float* mask2, float* mean_out, int total, int B, void* stream) {
+  if (!reward || !mask2 || total <= 0 || B <= 0) return SR_EINVAL;
+  SR_LAUNCH(reward_mask2_kernel, dim3(cdiv(total, B)), dim3(64), 0, (hipStream_t)stream, reward, mask2, mean_out, (const float*)nullptr, B,
+            total);
   SR_CHECK_LAUNCH();
   return SR_OK;
 }

@@ -846,7 +846,12 @@ def freematch_entropy(logits, mask, p_model, label_hist, grad_scale, loss_out, d
           B, C, int(accumulate), _s())
 
 
-def reward_mask2(reward, mask2, mean_out, groups, B, mean_in=None):
+def reward_mask2(reward, mask2, mean_out, groups, B, mean_in=None, total=None):
+    """total (rows in all, groups == ceil(total / B)): the last group holds the rows that are left and takes its own mean over them."""
+    if total is not None and total != groups * B:
+        assert mean_in is None and groups == -(-total // B)
+        _call("srhip_reward_mask2_ragged", _p(reward), _p(mask2), _p(mean_out), total, B, _s())
+        return
     _call("srhip_reward_mask2", _p(reward), _p(mask2), _p(mean_out), _p(mean_in), groups, B, _s())
 
 
@@ -947,6 +952,45 @@ def pl_monitor(pseudo, mask0, mask_kept, mask2, reward, idx_ulb, ulb_targets, P,
           int(ulb_targets.numel()), P, nu, C, _p(istate), _p(fstate), _s())
 
 
+# ---- scoring a whole unlabelled set (score_rows.hip) ----------------------------------------------
+SCORE_MODES = {"fixed": _lib.SCORE_FIXED, "flex": _lib.SCORE_FLEX, "free": _lib.SCORE_FREE, "soft": _lib.SCORE_SOFT}
+SCORE_COLUMNS = (("label", torch.int64), ("conf", torch.float32), ("margin", torch.float32), ("entropy", torch.float32),
+                 ("weight", torch.float32))                                   # what srhip_score_rows writes, dense [B]
+TABLE_COLUMNS = SCORE_COLUMNS + (("reward", torch.float32), ("reward_keep", torch.uint8), ("selected", torch.uint8),
+                                 ("count", torch.int32))                      # what srhip_score_commit scatters, [n]
+
+
+def score_rows(logits, mode, out, p_cutoff=0.0, classwise_acc=None, time_p=None, p_model=None, mu_var=None, n_sigma=0, da_p_model=None,
+               da_p_target=None, da_inited=None):
+    """One batch of logits (fp32 [B, C], rows may be strided) -> the five dense columns of SCORE_COLUMNS in ``out`` (a dict of [>= B] device
+    tensors): label / conf as ops.row_max gives them, margin, entropy, and the threshold rule's mask or weight from the state passed in, which
+    is only read (srhip_score_rows).  mode: 'fixed' | 'flex' | 'free' | 'soft' or the integer."""
+    z, ld = _rows(logits)
+    B, C = int(logits.shape[0]), int(logits.shape[1])
+    if _CHECK_ARGS:
+        for k, dt in SCORE_COLUMNS:
+            assert out[k].dtype == dt and out[k].numel() >= B and out[k].is_cuda and out[k].is_contiguous(), k
+    _call("srhip_score_rows", z, ld, B, C, SCORE_MODES.get(mode, mode), float(p_cutoff), _p(classwise_acc), _p(time_p), _p(p_model),
+          _p(mu_var), int(n_sigma), _p(da_p_model), _p(da_p_target), _p(da_inited), _p(out["label"]), _p(out["conf"]), _p(out["margin"]),
+          _p(out["entropy"]), _p(out["weight"]), _s())
+
+
+def score_commit(batch, reward, reward_keep, table, B, idx=None, row_offset=0):
+    """Scatter one scored batch (``batch``: the dict score_rows filled; reward fp32 [B]; reward_keep the fp32 mask ops.reward_mask2 wrote)
+    into ``table``, a dict of the [n] device columns of TABLE_COLUMNS, at idx[b] (int64, unique within the batch) or row_offset + b
+    (srhip_score_commit).  An index outside [0, n) is skipped and raises IndexError at the next ops.check_label_errors()."""
+    n = int(table["label"].numel())
+    if _CHECK_ARGS:
+        for k, dt in TABLE_COLUMNS:
+            assert table[k].dtype == dt and table[k].numel() == n and table[k].is_cuda and table[k].is_contiguous(), k
+        assert reward.dtype == torch.float32 and reward.numel() >= B and reward_keep.dtype == torch.float32 and reward_keep.numel() >= B
+        assert idx is None or (idx.dtype == torch.int64 and idx.numel() >= B)
+    _call("srhip_score_commit", _p(batch["label"]), _p(batch["conf"]), _p(batch["margin"]), _p(batch["entropy"]), _p(batch["weight"]),
+          _p(reward), _p(reward_keep), _p(idx), int(row_offset), B, n, _p(table["label"]), _p(table["conf"]), _p(table["margin"]),
+          _p(table["entropy"]), _p(table["weight"]), _p(table["reward"]), _p(table["reward_keep"]), _p(table["selected"]), _p(table["count"]),
+          _s())
+
+
 # ---- rewarder / generator ---------------------------------------------------------------------
 def rewarder_param_count(F, L):
     return int(_lib.lib().srhip_rewarder_param_count(F, L))
@@ -1006,6 +1050,9 @@ _LABEL_ERR = ("a label outside [0, label_dim) reached the rewarder's nn.Embeddin
               "an evaluation label outside [-1, num_classes) reached F.cross_entropy (algorithmbase.py:407)",
               "an idx_ulb entry outside [0, len(ulb_targets)) or a true label >= num_classes reached the pseudo-label monitor "
               "(monitor_pseudo_labels)")
+# bit 6 (srhip_score_commit), kept beside the tuple: its length is the number of bits the training step's launches can set
+_SCORE_ERR_BIT = 6
+_SCORE_ERR = "a row index outside [0, n) reached the pseudo-label table (score_unlabeled: idx_ulb, or more rows than the table holds)"
 
 
 def check_label_errors(reset=True):
@@ -1016,6 +1063,8 @@ def check_label_errors(reset=True):
     _call("srhip_label_error", ctypes.addressof(bits), int(reset), _s())
     _call("srhip_index_error", ctypes.addressof(ibits), int(reset), _s())
     msgs = [m for i, m in enumerate(_LABEL_ERR) if bits.value >> i & 1]
+    if bits.value >> _SCORE_ERR_BIT & 1:
+        msgs.append(_SCORE_ERR)
     if ibits.value:
         msgs.append("an idx_ulb entry outside [0, ulb_dest_len) reached FlexMatchThresholdingHook.update (srflexmatch/utils.py:59)")
     if msgs:
