@@ -219,6 +219,15 @@ int srhip_mlp_fused_proj(const float* x, float* x_out, const void* ao, const voi
                          int ao_scaled, const float* ln_gamma, const float* ln_beta, float eps, const void* W1, const float* b1, const void* W2,
                          const float* b2, const float* row_scale2, int rows_per_sample, void* ln_next, const float* next_gamma,
                          const float* next_beta, int M, int D, int Hd, void* stream);
+/* srhip_mlp_fused_proj over M rows that lie row_pitch elements apart in x, x_out and ao: logical row m at element m * row_pitch of each.  For the
+ * last block of a forward whose only reader is the head (srhip_cls_head_fwd reads row b * N of image b): M = images, rows_per_sample = 1,
+ * row_pitch = N * D computes the class-token rows in place and neither reads nor writes the rows in between.  Everything per row is
+ * srhip_mlp_fused_proj's, so a row's result is bit for bit the one of the dense launch that contains it.
+ * SR_EINVAL: row_pitch < D, row_pitch % 8 != 0 (16-byte row starts of the bf16 operand), ln_next with row_pitch != D. */
+int srhip_mlp_fused_proj_strided(const float* x, float* x_out, const void* ao, const void* Wp, const float* bp, const float* row_scale1,
+                                 int ao_scaled, const float* ln_gamma, const float* ln_beta, float eps, const void* W1, const float* b1,
+                                 const void* W2, const float* b2, const float* row_scale2, int rows_per_sample, void* ln_next,
+                                 const float* next_gamma, const float* next_beta, int M, int D, int Hd, int row_pitch, void* stream);
 
 /* Fused qkv projection + attention of a ViT block for rows without a backward: ao = softmax(q k^T * scale) v with [q | k | v] = xn Wqkv^T +
  * bqkv -- Attention.forward up to the output projection (semilearn/nets/vit/vit.py:93-104) on the norm1 output (:163) in ONE launch, one

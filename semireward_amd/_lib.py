@@ -48,6 +48,7 @@ SIGNATURES = {
     "srhip_attn_block_fused": (I, [P, P, P, P, P, P, I, I, I, I, F, P]),
     "srhip_gelu_eval": (I, [P, P, P, I, P]),
     "srhip_mlp_fused_proj": (I, [P, P, P, P, P, P, I, P, P, F, P, P, P, P, P, I, P, P, P, I, I, I, P]),
+    "srhip_mlp_fused_proj_strided": (I, [P, P, P, P, P, P, I, P, P, F, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
     "srhip_adam_bias_corrections": (I, [F, F, I, P]),
     "srhip_adamw_flat_dyn": (I, [P, P, P, P, P, P, P, I, P, P, P, F, F, F, Dbl, F, P, I, P]),
     "srhip_adam_flat_dyn": (I, [P, P, P, P, L, F, F, F, F, P, P]),

@@ -79,6 +79,9 @@ struct MlpArgs {
   const float *gamma_n, *beta_n;
   float eps;
   int M, Hd, rows_per_sample;
+  // PITCH variant of PROJ: logical row m of x, xo and ao lives at element m * pitch (one row per sample out of a [samples, tokens, D] buffer:
+  // pitch = tokens * D); everything per row is the plain PROJ kernel's, so a row's result does not depend on the launch that carries it
+  int pitch;
 };
 
 // DBG (tuning builds only, SRHIP_MLP_DEBUG): 1 = no GELU, 2 = no DMA / no vmcnt waits, 4 = no ds_reads, 8 = no MFMA
@@ -91,8 +94,10 @@ __device__ long long srhip_mlp_dbg[8 * 1024];
 // SPREAD: the ring refills are issued one per stage behind the stage's first MFMA half ("stage j asks for stage j + PD") instead of GS in a row
 // right behind the group barrier.  An LDS-DMA instruction blocks its wave for ~100 cycles, and behind a barrier all eight waves -- both waves of
 // every SIMD -- sit in that block together while the matrix pipe idles (measured on the producer / consumer kernel, profiles/r03_mlp_ps_*).
-template <int D_, int DBG, int GS, bool PROJ = false, int SPREAD = 0>
+// PITCH: an instantiation of its own, so that the dense PROJ kernel keeps the code (and the register allocation) it has without the field
+template <int D_, int DBG, int GS, bool PROJ = false, int SPREAD = 0, bool PITCH = false>
 __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(MlpArgs a) {
+  static_assert(PROJ || !PITCH, "the row pitch belongs to the PROJ variant");
   constexpr int KS1 = D_ / BK;            // 12 k-steps of GEMM1
   constexpr int KQ = 4;                   // k-steps per GEMM1 stage
   constexpr int G1S = 2 * (KS1 / KQ);     // 6 GEMM1 stages per chunk: 2 pair-groups x 3 k-ranges
@@ -170,6 +175,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(MlpArgs a) {
   const int fo1p = h1 * BK + ((lg ^ swz(h1)) << 3);
   const int fo1q = (h1 + 4) * BK + ((lg ^ swz(h1 + 4)) << 3);
 
+  const size_t rpitch = PITCH ? (size_t)a.pitch : (size_t)D_;      // elements between rows of x, xo and ao
   const int ntiles = (a.M + FBM - 1) / FBM;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int m = tile * FBM + wave * 16 + l15;
@@ -224,7 +230,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(MlpArgs a) {
     // PROJ: the attention output rows of the wave as MFMA B-fragments (lane holds ao[m][32 s + 8 g .. + 7])
     u32x4_t aof[PROJ ? KS1 : 1];
     if constexpr (PROJ) {
-      const bf16_t* ar = a.ao + (size_t)mc * D_ + 8 * lg;
+      const bf16_t* ar = a.ao + (size_t)mc * rpitch + 8 * lg;
 #pragma unroll
       for (int k = 0; k < KS1; ++k) aof[k] = *reinterpret_cast<const u32x4_t*>(ar + 32 * k);
     }
@@ -240,7 +246,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(MlpArgs a) {
     if constexpr (PROJ) {
       if (a.row_scale1) rs1v = a.row_scale1[mc / a.rows_per_sample];
       if (a.row_scale) rs2v = a.row_scale[mc / a.rows_per_sample];
-      const float* xr = a.x + (size_t)mc * D_ + 4 * lg;
+      const float* xr = a.x + (size_t)mc * rpitch + 4 * lg;
 #pragma unroll
       for (int t = 0; t < NT2; ++t) acc2[t] = *reinterpret_cast<const f32x4_t*>(xr + 16 * t);
       if (rs1v != 1.0f && !a.ao_scaled) {
@@ -509,7 +515,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(MlpArgs a) {
     MDBG_T(2);
     // ---- epilogue: lane holds y[m][16 t + 4 g + r]
     if (PROJ && a.ln_next) {                // wave-uniform: the rows leave as fp32 (residual stream) AND normalised for the next block
-      float* xw = a.xo + (size_t)mc * D_ + 4 * lg;
+      float* xw = a.xo + (size_t)mc * rpitch + 4 * lg;
       float sum = 0.f;
 #pragma unroll
       for (int t = 0; t < NT2; ++t) {
@@ -552,7 +558,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_kernel(MlpArgs a) {
         if (m < a.M) *reinterpret_cast<u32x4_t*>(lw + 32 * sI) = u32x4_t{out4[0], out4[1], out4[2], out4[3]};
       }
     } else if (PROJ) {
-      float* xw = a.xo + (size_t)mc * D_ + 4 * lg;
+      float* xw = a.xo + (size_t)mc * rpitch + 4 * lg;
       if (m < a.M) {
 #pragma unroll
         for (int t = 0; t < NT2; ++t) *reinterpret_cast<f32x4_t*>(xw + 16 * t) = acc2[t];
@@ -621,6 +627,7 @@ extern "C" int srhip_mlp_fused(const float* x, float* x_out, const float* ln_gam
   a.W1 = (const bf16_t*)W1; a.W2 = (const bf16_t*)W2; a.eps = eps; a.M = M; a.Hd = Hd;
   a.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1;
   a.ao = nullptr; a.Wp = nullptr; a.bp = nullptr; a.row_scale1 = nullptr; a.ao_scaled = 0; a.ln_next = nullptr; a.gamma_n = a.beta_n = nullptr;
+  a.pitch = D;
   const size_t smem = (size_t)NS * TILE_EL * sizeof(bf16_t) + (size_t)(Hd + 6 * D) * sizeof(float);
   void (*kern)(MlpArgs) = mlp_fused_kernel<384, 0, 4>;
 #ifdef SRHIP_TUNING
@@ -648,10 +655,11 @@ extern "C" int srhip_mlp_fused(const float* x, float* x_out, const float* ln_gam
 // (vit.py:163 tail: proj :105-106 + drop_path1 + residual, and :165).  Saves the proj GEMM launch and two reads + a write of the residual stream:
 // x enters as the start value of the accumulators and x1 stays there.  ao_scaled != 0: ao already carries row_scale1 (only bp is scaled here).
 // ln_next != NULL: also LayerNorm(x_out) with (next_gamma, next_beta) -- the next block's norm1 (vit.py:163) -- as bf16 [M, D].
-extern "C" int srhip_mlp_fused_proj(const float* x, float* x_out, const void* ao, const void* Wp, const float* bp, const float* row_scale1,
-                                    int ao_scaled, const float* ln_gamma, const float* ln_beta, float eps, const void* W1, const float* b1, const void* W2,
-                                    const float* b2, const float* row_scale2, int rows_per_sample, void* ln_next, const float* next_gamma,
-                                    const float* next_beta, int M, int D, int Hd, void* stream) {
+// row_pitch == 0: rows packed at D (the dense kernel); otherwise the PITCH instantiation
+static int mlp_fused_proj_launch(const float* x, float* x_out, const void* ao, const void* Wp, const float* bp, const float* row_scale1,
+                                 int ao_scaled, const float* ln_gamma, const float* ln_beta, float eps, const void* W1, const float* b1, const void* W2,
+                                 const float* b2, const float* row_scale2, int rows_per_sample, void* ln_next, const float* next_gamma,
+                                 const float* next_beta, int M, int D, int Hd, int row_pitch, void* stream) {
   if (!x || !x_out || !ao || !Wp || !bp || !ln_gamma || !ln_beta || !W1 || !b1 || !W2 || !b2 || M <= 0) return SR_EINVAL;
   if (ln_next && (!next_gamma || !next_beta || ((uintptr_t)ln_next & 15))) return SR_EINVAL;
   if (D != 384 || Hd < 128 || (Hd % RT) || Hd > 4096) return SR_EINVAL;
@@ -664,15 +672,36 @@ extern "C" int srhip_mlp_fused_proj(const float* x, float* x_out, const void* ao
   a.W1 = (const bf16_t*)W1; a.W2 = (const bf16_t*)W2; a.eps = eps; a.M = M; a.Hd = Hd;
   a.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1;
   a.ao = (const bf16_t*)ao; a.Wp = (const bf16_t*)Wp; a.bp = bp; a.row_scale1 = row_scale1; a.ao_scaled = ao_scaled;
-  a.ln_next = (bf16_t*)ln_next; a.gamma_n = next_gamma; a.beta_n = next_beta;
+  a.ln_next = (bf16_t*)ln_next; a.gamma_n = next_gamma; a.beta_n = next_beta; a.pitch = row_pitch ? row_pitch : D;
   const size_t smem = (size_t)NS * TILE_EL * sizeof(bf16_t) + (size_t)(Hd + 6 * D) * sizeof(float);
   // SRHIP_MLP_SPREAD=0: all GS refills of a group right behind its barrier (the round-2 schedule; A/B on one box: 104 -> 99.5 us per 105-image
   // launch, 1547 -> 1574 img/s on the step)
   static const int spread = SR_TUNE_ENV("SRHIP_MLP_SPREAD") ? atoi(SR_TUNE_ENV("SRHIP_MLP_SPREAD")) : 1;
   void (*kern)(MlpArgs) = spread ? mlp_fused_kernel<384, 0, 4, true, 1> : mlp_fused_kernel<384, 0, 4, true, 0>;
+  if (row_pitch) kern = mlp_fused_kernel<384, 0, 4, true, 1, true>;
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   const int ntiles = cdiv(M, FBM);
   SR_LAUNCH(kern, dim3(min(ntiles, 256)), dim3(512), smem, (hipStream_t)stream, a);
   SR_CHECK_LAUNCH();
   return SR_OK;
+}
+
+extern "C" int srhip_mlp_fused_proj(const float* x, float* x_out, const void* ao, const void* Wp, const float* bp, const float* row_scale1,
+                                    int ao_scaled, const float* ln_gamma, const float* ln_beta, float eps, const void* W1, const float* b1, const void* W2,
+                                    const float* b2, const float* row_scale2, int rows_per_sample, void* ln_next, const float* next_gamma,
+                                    const float* next_beta, int M, int D, int Hd, void* stream) {
+  return mlp_fused_proj_launch(x, x_out, ao, Wp, bp, row_scale1, ao_scaled, ln_gamma, ln_beta, eps, W1, b1, W2, b2, row_scale2, rows_per_sample, ln_next,
+                               next_gamma, next_beta, M, D, Hd, 0, stream);
+}
+
+// srhip_mlp_fused_proj over M rows that lie row_pitch elements apart in x, x_out and ao (the class-token rows of a [samples, tokens, D] residual
+// stream: M = samples, rows_per_sample = 1, row_pitch = tokens * D).  Rows in between are neither read nor written.
+extern "C" int srhip_mlp_fused_proj_strided(const float* x, float* x_out, const void* ao, const void* Wp, const float* bp, const float* row_scale1,
+                                            int ao_scaled, const float* ln_gamma, const float* ln_beta, float eps, const void* W1, const float* b1,
+                                            const void* W2, const float* b2, const float* row_scale2, int rows_per_sample, void* ln_next,
+                                            const float* next_gamma, const float* next_beta, int M, int D, int Hd, int row_pitch, void* stream) {
+  if (row_pitch < D || (row_pitch % 8) != 0) return SR_EINVAL;     // rows must not overlap; 16-byte row starts of the fp32 and the bf16 operand
+  if (ln_next && row_pitch != D) return SR_EINVAL;                 // the next block's norm1 rows are packed: only a dense launch writes them
+  return mlp_fused_proj_launch(x, x_out, ao, Wp, bp, row_scale1, ao_scaled, ln_gamma, ln_beta, eps, W1, b1, W2, b2, row_scale2, rows_per_sample, ln_next,
+                               next_gamma, next_beta, M, D, Hd, row_pitch, stream);
 }

@@ -67,6 +67,8 @@ _FUSED_MLP = True          # LN2 + fc1 + GELU + fc2 + residual as one launch
 _FUSED_ATTN = True         # qkv Linear + attention as one launch
 _FUSED_PROJ = True         # attention projection + residual inside the fused MLP launch
 _FUSED_NEXT_LN = True      # ... which then also writes the next block's norm1 output
+# the head reads one row per image (the class token): behind the LAST block's attention the fused proj + MLP launch runs those rows only
+_LAST_BLOCK_CLASS_ROWS = True
 # the fused kernel owns a CU per 128-row tile for ~90 us whatever the launch size: below ~half a chip of tiles (the 8 inference images of the
 # pre-start_timing regime = 17 tiles) LayerNorm + two 64x64-tiled GEMMs spread over all CUs are faster
 _FUSED_MLP_MIN_ROWS = 16384
@@ -328,11 +330,15 @@ class VisionTransformer(ModuleSurface):
                 # block's norm1 output (the operand of its fused qkv + attention launch) when there is a next block
                 nb = "blocks.%d." % (i + 1)
                 ln_ready = _FUSED_NEXT_LN and i + 1 < cfg.depth
+                # last block: nothing reads its non-class rows of x (_head takes row b * N of image / node b) and a row's values do not depend
+                # on the launch that carries it, so row b of the launch = row b * N of x and ao, in place: B rows instead of B * N
+                class_rows = _LAST_BLOCK_CLASS_ROWS and i == cfg.depth - 1
+                rps, rows, pitch = (1, B, N * D) if class_rows else (N, M, None)
                 ops.mlp_fused_proj(x, ao, P(b + "attn.proj.weight", wb), P(b + "attn.proj.bias"), s1, P(b + "norm2.weight"),
                                    P(b + "norm2.bias"), cfg.eps, P(b + "mlp.fc1.weight", wb), P(b + "mlp.fc1.bias"),
-                                   P(b + "mlp.fc2.weight", wb), P(b + "mlp.fc2.bias"), s2, N, M, D, Hd,
+                                   P(b + "mlp.fc2.weight", wb), P(b + "mlp.fc2.bias"), s2, rps, rows, D, Hd,
                                    ln_next=ln if ln_ready else None, next_gamma=P(nb + "norm1.weight") if ln_ready else None,
-                                   next_beta=P(nb + "norm1.bias") if ln_ready else None, ao_scaled=ao_scaled)
+                                   next_beta=P(nb + "norm1.bias") if ln_ready else None, ao_scaled=ao_scaled, row_pitch=pitch)
             else:
                 ops.gemm_nt(ops.EPI_RESID_F32, ao, P(b + "attn.proj.weight", wb), x, M, D, D, bias=P(b + "attn.proj.bias"),
                             row_scale=s1, rows_per_sample=N, **gp)

@@ -565,18 +565,26 @@ def mlp_fused(x, gamma, beta, eps, W1, b1, W2, b2, row_scale, rows_per_sample, M
 
 
 def mlp_fused_proj(x, ao, Wp, bp, row_scale1, gamma, beta, eps, W1, b1, W2, b2, row_scale2, rows_per_sample, M, D, Hd, x_out=None,
-                   ln_next=None, next_gamma=None, next_beta=None, ao_scaled=False):
+                   ln_next=None, next_gamma=None, next_beta=None, ao_scaled=False, row_pitch=None):
     """x_out (default: x, in place) = x1 + row_scale2 * (fc2(gelu(fc1(LN(x1)))) + b2) with x1 = x + row_scale1 * (ao Wp^T + bp): the attention
     projection, both residuals and the MLP half of a block in ONE launch (rows without a backward).  ln_next (bf16 [M, D]): also
-    LayerNorm(x_out) with the next block's norm1 affine.  ao_scaled: ao already carries row_scale1 (attn_block_fused out_scale)."""
+    LayerNorm(x_out) with the next block's norm1 affine.  ao_scaled: ao already carries row_scale1 (attn_block_fused out_scale).
+    row_pitch (elements): the M rows lie that far apart in x, x_out and ao (srhip_mlp_fused_proj_strided); rows in between are untouched."""
     args = (_p(x), _p(x_out if x_out is not None else x), _p(ao), _p(Wp), _p(bp), _p(row_scale1), int(bool(ao_scaled)), _p(gamma), _p(beta), eps,
             _p(W1), _p(b1),
             _p(W2), _p(b2), _p(row_scale2), rows_per_sample, _p(ln_next), _p(next_gamma), _p(next_beta), M, D, Hd)
     if _PROFILE is not None:
         # algorithmic: fc1 + fc2 + proj products; bytes: x in, x out (fp32; x1 never leaves the accumulators), ao in (bf16), [next norm1
         # output out (bf16)], the weights once
-        _PROFILE.timed("srhip_mlp_fused_proj", (*args, _s(),), 4.0 * M * D * Hd + 2.0 * M * D * D, "mlp_fused_kernel<384, 0, 4, true, 1>",
-                              8.0 * M * D + 2.0 * M * D + (2.0 * M * D if ln_next is not None else 0.0) + 4.0 * D * Hd + 2.0 * D * D)
+        nbytes = 8.0 * M * D + 2.0 * M * D + (2.0 * M * D if ln_next is not None else 0.0) + 4.0 * D * Hd + 2.0 * D * D
+        if row_pitch is not None:       # a record of its own: the dense kernel's roofline line stays comparable with earlier ones
+            _PROFILE.timed("srhip_mlp_fused_proj_strided", (*args, int(row_pitch), _s(),), 4.0 * M * D * Hd + 2.0 * M * D * D,
+                           "mlp_fused_kernel<384, 0, 4, true, 1> class rows", nbytes)
+            return
+        _PROFILE.timed("srhip_mlp_fused_proj", (*args, _s(),), 4.0 * M * D * Hd + 2.0 * M * D * D, "mlp_fused_kernel<384, 0, 4, true, 1>", nbytes)
+        return
+    if row_pitch is not None:
+        _call("srhip_mlp_fused_proj_strided", *args, int(row_pitch), _s())
         return
     _call("srhip_mlp_fused_proj", *args, _s())
 
