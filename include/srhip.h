@@ -869,6 +869,19 @@ int srhip_wrn_conv_bn_passes(const float* xin, int in_mode, const float* in_mean
                              const float* in_beta, float in_eps, float slope, float* pub_mean, float* pub_invstd, float* running_mean,
                              float* running_var, float momentum, int update_running, const void* Wb, const float* resid, float* y, int B, int H,
                              int W, int Cin, int Cout, int ksize, int stride, int Kpad, double* acc_out, int stat_ranks, int passes, void* stream);
+/* "All groups" running statistics for a shared-launch forward: with update_running = 0 in srhip_wrn_conv_bn_passes / srhip_wrn_head_passes,
+ * ONE launch after the forward moves the running statistics of every BatchNorm of the table once per statistics group, in group order --
+ * running = (1 - momentum) * running + momentum * stat_g for g = 0 .. groups - 1, in fp32, stat_g = mean / unbiased variance from group g's
+ * fp64 sums (under SyncBatchNorm the exchanged sums; rows = this rank's rows * ranks).  This is what `groups` model() calls in training mode
+ * without Bn_Controller do (semilearn/algorithms/srfixmatch/fixmatch.py:62-146 forwards the concatenated batch K + 1 times per step).  Entry:
+ * acc = the accumulators [groups, srhip_bn_acc_doubles(C)] the forward filled (complete once its last launch is enqueued), C <= 256.  One
+ * workgroup per entry, one thread per channel carries the chain (no atomics, no reduction across threads); a step is the expression of the
+ * publishing launch, so groups = 1 gives the bits of update_running = 1 there. */
+typedef struct srhip_bn_chain_desc {
+  const double* acc; float* running_mean; float* running_var;
+  int C, rows;
+} srhip_bn_chain_desc;                   /* 32 bytes */
+int srhip_bn_running_chain(const srhip_bn_chain_desc* desc_dev, int n, int groups, float momentum, void* stream);
 /* wrn_head : the network's tail (wrn.py:119-126) in one launch: feat [B, C] = mean over the HW2 pixels of LeakyReLU(BatchNorm(x)), logits [B, K] =
  * feat Wc^T + bc; in_mode 0 / 1 / 3 and the publishing arguments as for wrn_conv_bn (workgroup 0 publishes).  C <= 256. */
 int srhip_wrn_head(const float* x, int in_mode, const float* in_mean, const float* in_isd, const double* in_acc, const float* gamma,

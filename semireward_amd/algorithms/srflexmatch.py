@@ -365,6 +365,14 @@ def backbone_class(net_builder):
     return found[0] if len(found) == 1 else None
 
 
+def _refuse_split_calls_on_batchnorm(args, net_cls):
+    """``use_cat: False`` forwards x_lb, x_ulb_w and x_ulb_s in three model() calls per pass (fixmatch.py:118-128): on a BatchNorm backbone that
+    is three statistics groups per pass, which the step does not build.  A ValueError that names the key, before any device work."""
+    if net_cls is not None and getattr(net_cls, "couples_batch_rows", False) and not getattr(args, "use_cat", True):
+        raise ValueError("use_cat: False with a BatchNorm backbone (%s): every pass would be three BatchNorm statistics groups, which this step "
+                         "does not build; the classic_cv configs set use_cat: True" % net_cls.__name__)
+
+
 def read_rows_precision(args, net_cls=None):
     """Numeric mode of the rows that decide masks, pseudo labels and rewards (the weak rows of every pass): ``args.read_rows_precision``, else
     the environment variable SR_READ_ROWS_PRECISION, else "bf16".
@@ -439,10 +447,12 @@ class SRConsistencyBase(AlgorithmBase):
         self.read_rows_precision = read_rows_precision(args, backbone_class(net_builder))
         self.grad_rows_precision = grad_rows_precision(args, backbone_class(net_builder))
         self.share_pass_prefixes = share_pass_prefixes(args, backbone_class(net_builder))
+        _refuse_split_calls_on_batchnorm(args, backbone_class(net_builder))
         super().__init__(args, net_builder, tb_log, logger)
         read_rows_precision(argparse.Namespace(read_rows_precision=self.read_rows_precision), type(self.model))
         grad_rows_precision(argparse.Namespace(grad_rows_precision=self.grad_rows_precision), type(self.model))
         share_pass_prefixes(argparse.Namespace(share_pass_prefixes=self.share_pass_prefixes), type(self.model))
+        _refuse_split_calls_on_batchnorm(args, type(self.model))
         if self.grad_rows_precision == "bf16x3":
             self.model.grad_rows_precision = "bf16x3"        # the opt-in of the backbone's saved split-bf16 forward
         self._init_thresholds(args)
@@ -706,6 +716,17 @@ class SRConsistencyBase(AlgorithmBase):
         return mk(False)
 
     def _forward_passes(self, imgs, nl, nu, K):
+        if self.model.couples_batch_rows:
+            # BatchNorm couples the rows: a pass is ONE statistics group over cat(x_lb, x_ulb_w, x_ulb_s) that moves the running statistics
+            # (fixmatch.py:62-146: K + 1 model() calls in training mode, no Bn_Controller) -- no column plan, no side stream, no deferred rows;
+            # the K + 1 groups share the launches (WideResNet.forward_cat_passes) and ctx = the saved groups (pass 0, last pass).
+            # What the rest of _train_step does on this branch: _join_grad and _join_deferred are inert (this forward leaves nothing pending:
+            # _grad_pending and _rest_done stay None); gemm_small_max_grid is not set.  The BACKBONE uses the step's stream only.  The rewarder's
+            # max_reward scoring and the stage-1 rewarder update still run on the side stream under the backbone's backward, as on every
+            # backbone: they read the finished feature table and the rewarder, nothing the backward touches, and the step's stream waits for
+            # them before anything else reads the rewarder.
+            lg, ft, ctxs = self.model.forward_cat_passes(imgs, K + 1, tag="cat")
+            return lg.view(K + 1, imgs.shape[0], -1), ft.view(K + 1, imgs.shape[0], -1), ctxs
         key = (nl, nu, K, bool(self.use_cat), self.elide_unread_rows)
         if key in self._untuned and self.dp.settled:
             self._untuned.discard(key)
@@ -797,7 +818,8 @@ class SRConsistencyBase(AlgorithmBase):
         # (fewer, fatter workgroups win: 4.86 vs 4.95 ms per step); with K = 0 the chain has the chip to itself (64 x 64 tiles: 3.21 vs 3.57 ms)
         # (process-wide library setting: restored when the step returns -- train_step's wrapper -- so that evaluate(), the EMA forward and
         # anything else that runs between steps picks its tiles independently of which step ran last)
-        ops.gemm_small_max_grid(ops.GEMM_SMALL_CONTENDED if (K > 0 and self.defer_unread_rows) else ops.GEMM_SMALL_ALONE)
+        if not self.model.couples_batch_rows:
+            ops.gemm_small_max_grid(ops.GEMM_SMALL_CONTENDED if (K > 0 and self.defer_unread_rows) else ops.GEMM_SMALL_ALONE)
         ph = self._phase_mark if _PHASES else (lambda name: None)
         ph("start")
         L, Fe, ctx = self._forward_passes(imgs, nl, nu, K)
@@ -893,7 +915,23 @@ class SRConsistencyBase(AlgorithmBase):
                         self._sr_update(fx, gen, y_lb)                                            # :194-208
                     stage1_done = torch.cuda.Event()
                     stage1_done.record(side)
-        self.model.backward(ctx, dl_buf if (two_blocks and len(dl_all) == 2) else torch.cat(dl_all))
+        if self.model.couples_batch_rows:
+            # whole-batch upstream gradients per saved group (BatchNorm couples the rows), zeros where a row has none: pass 0 gets the labelled
+            # rows (+ FreeMatch's fairness rows when K > 0), the last pass the strong rows; K = 0: one group with both
+            d0 = torch.zeros(Bt, C, dtype=torch.float32, device=self.device)
+            d0[:nl].copy_(dl_lb)
+            if len(ctx) == 1:
+                d0[nl + nu:].copy_(dl_s)
+            else:
+                if len(dl_all) == 3:
+                    d0[nl + nu:].copy_(dl_all[1])
+                dK = torch.zeros(Bt, C, dtype=torch.float32, device=self.device)
+                dK[nl + nu:].copy_(dl_s)
+            self.model.backward(ctx[0], d0)
+            if len(ctx) > 1:
+                self.model.backward(ctx[1], dK)
+        else:
+            self.model.backward(ctx, dl_buf if (two_blocks and len(dl_all) == 2) else torch.cat(dl_all))
         if score_done is not None:
             torch.cuda.current_stream().wait_event(score_done)
         if stage1_done is not None:

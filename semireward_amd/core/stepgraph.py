@@ -94,6 +94,9 @@ class StepGraph:
     def __init__(self, algorithm, warm=2):
         if not getattr(algorithm, "graph_safe", False):
             raise ValueError("%s keeps per-step state in Python objects: not capturable" % type(algorithm).__name__)
+        if getattr(getattr(algorithm, "model", None), "couples_batch_rows", False):
+            raise ValueError("%s on a BatchNorm backbone: its steps are not captured (num_batches_tracked and the per-K buffer sets of the shared "
+                             "launches live outside a graph)" % type(algorithm).__name__)
         self.alg, self.warm = algorithm, warm
         self.scal = StepScalars(algorithm.device)
         algorithm.step_scalars = algorithm.model.step_scalars = self.scal

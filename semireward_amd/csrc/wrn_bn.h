@@ -55,18 +55,36 @@ __device__ __forceinline__ bool bn_arrive_and_fold(double* __restrict__ ws, doub
   return true;
 }
 
+// One statistics group from its fp64 sums, and one step of the running update -- the ONE spelling of these expressions, shared by every launch
+// that publishes (bn_finalize) and by the launch that walks all groups of a forward (bn_running_chain_kernel, wrn_ops.hip).  The contraction is
+// pinned, so the bits do not depend on what the compiler fuses in the surrounding code: the variance is one fused multiply-add in fp64, a
+// running step two separately rounded fp32 products and their sum.
+__device__ __forceinline__ void bn_group_stat(double s1, double s2, int rows, double& m, double& v) {
+  m = s1 / rows;
+  v = fma(-m, m, s2 / rows);
+}
+__device__ __forceinline__ float bn_unbiased_var(double v, int rows) {
+  return (float)((v > 0.0 ? v : 0.0) * ((double)rows / (double)(rows > 1 ? rows - 1 : 1)));
+}
+__device__ __forceinline__ float bn_running_step(float running, float momentum, float stat) {
+#pragma clang fp contract(off)
+  const float a = (1.0f - momentum) * running, b = momentum * stat;
+  return a + b;
+}
+
 // mean / invstd of the batch (biased variance) and the running update (unbiased variance), as bn_apply_kernel computes them
 __device__ __forceinline__ void bn_finalize(const double* red2c, int C, int rows, const BnFinal& f) {
   if (!f.out_mean) return;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    const double m = red2c[c] / rows, v = red2c[C + c] / rows - m * m;
+    double m, v;
+    bn_group_stat(red2c[c], red2c[C + c], rows, m, v);
     const float mu = (float)m, var = (float)(v > 0.0 ? v : 0.0);
     f.out_mean[c] = mu;
     f.out_invstd[c] = 1.0f / sqrtf(var + f.eps);
     if (f.update_running) {
-      const float unb = (float)((v > 0.0 ? v : 0.0) * ((double)rows / (double)(rows > 1 ? rows - 1 : 1)));
-      f.running_mean[c] = (1.0f - f.momentum) * f.running_mean[c] + f.momentum * mu;
-      f.running_var[c] = (1.0f - f.momentum) * f.running_var[c] + f.momentum * unb;
+      const float unb = bn_unbiased_var(v, rows);
+      f.running_mean[c] = bn_running_step(f.running_mean[c], f.momentum, mu);
+      f.running_var[c] = bn_running_step(f.running_var[c], f.momentum, unb);
     }
   }
 }

@@ -592,6 +592,42 @@ extern "C" int srhip_bn_fold(const double* acc, double rows_total, float eps, fl
   return SR_OK;
 }
 
+namespace {
+
+// Every statistics group of a shared-launch forward moves the running statistics, in group order (srhip_bn_running_chain, include/srhip.h).
+// One workgroup per BatchNorm of the table, one thread per channel: the chain running <- (1 - m) running + m stat_g is carried in registers,
+// so there is no atomic and no reduction across threads.  The copies are added in bn_arrive_and_fold's order and a step is bn_finalize's
+// own helper (wrn_bn.h: bn_group_stat / bn_running_step): one group gives the bits of the publishing launch's own update.
+__global__ __launch_bounds__(256) void bn_running_chain_kernel(const srhip_bn_chain_desc* __restrict__ desc, int groups, float momentum) {
+  const srhip_bn_chain_desc d = desc[blockIdx.x];
+  const int C = d.C, rows = d.rows, c = threadIdx.x;
+  if (c >= C) return;
+  float rm = d.running_mean[c], rv = d.running_var[c];
+  for (int g = 0; g < groups; ++g) {
+    const double* ag = d.acc + (size_t)g * BN_COPIES * 2 * C;
+    double u1[BN_COPIES], u2[BN_COPIES], t1 = 0.0, t2 = 0.0;
+#pragma unroll
+    for (int q = 0; q < BN_COPIES; ++q) { u1[q] = ag[(size_t)q * 2 * C + c]; u2[q] = ag[(size_t)q * 2 * C + C + c]; }
+#pragma unroll
+    for (int q = 0; q < BN_COPIES; ++q) { t1 += u1[q]; t2 += u2[q]; }
+    double m, v;
+    bn_group_stat(t1, t2, rows, m, v);                     // (wrn_bn.h: the expressions bn_finalize uses, contraction pinned)
+    rm = bn_running_step(rm, momentum, (float)m);
+    rv = bn_running_step(rv, momentum, bn_unbiased_var(v, rows));
+  }
+  d.running_mean[c] = rm;
+  d.running_var[c] = rv;
+}
+
+}  // namespace
+
+extern "C" int srhip_bn_running_chain(const srhip_bn_chain_desc* desc_dev, int n, int groups, float momentum, void* stream) {
+  if (!desc_dev || n <= 0 || groups <= 0) return SR_EINVAL;
+  SR_LAUNCH(bn_running_chain_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, desc_dev, groups, momentum);
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+
 extern "C" int srhip_bn_bwd_reduce(const float* dact, const float* x, const float* save_mean, const float* save_invstd, const float* gamma,
                                    const float* beta, float slope, double* ws, int rows, int C, void* stream) {
   if (!dact || !x || !save_mean || !save_invstd || !gamma || !beta || !ws || rows <= 0 || C <= 0 || C > 256 || (256 % C)) return SR_EINVAL;

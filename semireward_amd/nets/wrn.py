@@ -246,11 +246,12 @@ class WideResNet(ModuleSurface):
                                "exchange assumes equal row counts on every rank (a last partial batch or an uneven split)")
 
     def _conv_bn(self, wname, xin, in_bn, raw, B, H, W, stride, out, tag, train, update, resid=None, next_bn=None, publish=False, passes=1,
-                 accs=None):
+                 accs=None, chain=None):
         """out = conv(LeakyReLU(BN_in(xin))) (+ resid) -- or conv(xin) when ``raw`` -- and, in training mode, the sums of ``out`` added into the
         accumulator of ``next_bn`` (then exchanged between the ranks).  Training mode folds in_bn's statistics from its accumulator; ``publish``:
         this launch also writes in_bn's (mean, invstd) for the backward and moves its running statistics.  Returns in_bn's statistics buffers
-        (None in eval mode)."""
+        (None in eval mode).  ``chain``: a list that collects (BatchNorm, channels, statistics rows) of the publishing launches for
+        _running_chain."""
         c = self.convs[wname]
         P = self.p
         g, bt, eps = P(in_bn + ".weight"), P(in_bn + ".bias"), self.eps[in_bn]
@@ -267,11 +268,28 @@ class WideResNet(ModuleSurface):
         ops.wrn_conv_bn(xin, mode, stats, acc, g, bt, eps, SLOPE, c["Wb"], resid, out, B, H, W, c["cin"], c["cout"], c["k"], stride, c["Kp"],
                         publish=pub, running=(self.buffers[in_bn + ".running_mean"], self.buffers[in_bn + ".running_var"]) if pub else None,
                         momentum=MOMENTUM, update_running=update, acc_out=acc_out, stat_ranks=self.stat_ranks, passes=passes)
+        if pub and chain is not None:
+            chain.append((in_bn, c["cin"], B * H * W * self.stat_ranks))
         if acc_out is not None:
             self._sync_acc(next_bn, accs)
         return st
 
-    def forward_features(self, img, img_index=None, droppath=None, save=False, update_stats=True, tag=None, B=None, passes=1, first_img=None):
+    def _running_chain(self, chain, accs, G, tag):
+        """All G statistics groups of a shared-launch forward move the running statistics, in pass order: one launch over a table of this
+        forward's BatchNorms (ops.bn_running_chain), enqueued behind the forward -- every accumulator is complete (and exchanged) by then."""
+        key = ("bn_chain", tag, G)
+        sig = tuple((n, C, rows, int(accs[n].data_ptr()), int(self.buffers[n + ".running_mean"].data_ptr()),
+                     int(self.buffers[n + ".running_var"].data_ptr())) for n, C, rows in chain)
+        ent = self._buf_cache.get(key)
+        if ent is None or ent[0] != sig:          # (raw addresses and row counts: rebuilt when any of them changes)
+            ent = (sig, ops.make_bn_chain_desc([(accs[n], self.buffers[n + ".running_mean"], self.buffers[n + ".running_var"], C, rows)
+                                                for n, C, rows in chain], self.device))
+            self._buf_cache[key] = ent
+        self.chain_rows = {n: rows for n, _, rows in chain}      # (tests: the statistics rows of every BatchNorm of the latest forward)
+        ops.bn_running_chain(ent[1][0], ent[1][1], G, MOMENTUM)
+
+    def forward_features(self, img, img_index=None, droppath=None, save=False, update_stats=True, tag=None, B=None, passes=1, first_img=None,
+                         all_groups=False, keep_first=False):
         """img fp32 [B,3,H,W] (NCHW as the loaders deliver it).  Returns (logits [B,C], feat [B,F], ctx or None).
         ``update_stats=False`` = forward under Bn_Controller.freeze_bn.  ``tag`` names the activation buffer set (two saved graphs of
         a step must not share buffers).
@@ -282,7 +300,11 @@ class WideResNet(ModuleSurface):
         srpseudolabel.py:59-90 forwards x_ulb_w K + 1 times per step).  Returns logits [G * B, C], feat [G * B, F] in pass order;
         ``save`` keeps the LAST pass for a backward.  ``first_img`` (same shape as img): pass 0 forwards THAT batch instead -- the labelled
         batch of the step, the one model() call that moves the running statistics (``update_stats`` then applies to pass 0 alone, which is
-        what the kernels implement) -- and ``save`` keeps it as well: ctx = (ctx of pass 0, ctx of the last pass)."""
+        what the kernels implement) -- and ``save`` keeps it as well: ctx = (ctx of pass 0, ctx of the last pass).
+        ``all_groups`` (with update_stats, no first_img): EVERY pass moves the running statistics, in pass order, and num_batches_tracked
+        advances by G -- G model() calls in training mode with no Bn_Controller (srfixmatch / srflexmatch / srfreematch / srsoftmatch).  The
+        convolution launches then leave the running statistics alone and one launch behind the forward walks the groups (_running_chain).
+        ``keep_first`` (save, G > 1): pass 0 is kept for a backward too, ctx = (ctx of pass 0, ctx of the last pass) as for first_img."""
         assert img_index is None and droppath is None, "WideResNet has no DropPath and takes whole batches (BatchNorm couples the rows)"
         B, _, H, W = img.shape
         G = int(passes)
@@ -290,9 +312,15 @@ class WideResNet(ModuleSurface):
         train = self.training
         upd = bool(train and update_stats)
         assert train or not save, "the backward needs a training-mode forward (batch statistics)"
-        assert G == 1 or (train and (not upd or first_img is not None)), \
-            "passes > 1: batch statistics per pass; only a first_img pass may move the running statistics (the others run under Bn_Controller.freeze_bn)"
+        allg = bool(all_groups)
+        assert not allg or (upd and first_img is None), "all_groups: a training-mode forward that moves the running statistics, without first_img"
+        assert G == 1 or (train and (not upd or first_img is not None or allg)), \
+            "passes > 1: batch statistics per pass; a first_img pass or all_groups may move the running statistics (else Bn_Controller.freeze_bn)"
         assert first_img is None or (G > 1 and tuple(first_img.shape) == tuple(img.shape))
+        keep_first = bool(keep_first and save and G > 1 and first_img is None)
+        two = first_img is not None or keep_first
+        chain = [] if allg else None
+        kupd = upd and not allg                               # what the convolution / head launches do to the running statistics themselves
         f32 = torch.float32
         last = (lambda t, rows: t) if G == 1 else (lambda t, rows: t[(G - 1) * rows:])      # the pass a save=True forward keeps
         a0 = self._buf((tag, "in"), (B, H, W, 3), torch.bfloat16)
@@ -308,7 +336,7 @@ class WideResNet(ModuleSurface):
         if save:
             ctx = WrnContext()
             ctx.B, ctx.H, ctx.W, ctx.tag, ctx.stem, ctx.blocks = B, H, W, tag, dict(col=col0), []
-            if first_img is not None:
+            if two:
                 ctx_f = WrnContext()
                 ctx_f.B, ctx_f.H, ctx_f.W, ctx_f.tag, ctx_f.stem, ctx_f.blocks = B, H, W, tag + ":first", dict(col=colf), []
         h, w = H, W
@@ -337,17 +365,17 @@ class WideResNet(ModuleSurface):
             ho, wo = (h + 2 - 3) // stride + 1, (w + 2 - 3) // stride + 1
             rows_out = B * ho * wo
             c1 = self._buf((tag, p, "c1"), (G * rows_out, cout), f32)
-            kw = dict(passes=G, accs=accs)
+            kw = dict(passes=G, accs=accs, chain=chain)
             # conv1 reads x through bn1 (folding / publishing its statistics) and leaves the sums of its output for bn2
-            st1 = self._conv_bn(p + "conv1.weight", out, p + "bn1", raw, B, h, w, stride, c1, tag, train, upd, next_bn=p + "bn2", publish=True, **kw)
+            st1 = self._conv_bn(p + "conv1.weight", out, p + "bn1", raw, B, h, w, stride, c1, tag, train, kupd, next_bn=p + "bn2", publish=True, **kw)
             if equal:
                 sc = out
             else:
                 sc = self._buf((tag, p, "sc"), (G * rows_out, cout), f32)
-                self._conv_bn(p + "convShortcut.weight", out, p + "bn1", raw, B, h, w, stride, sc, tag, train, upd, **kw)
+                self._conv_bn(p + "convShortcut.weight", out, p + "bn1", raw, B, h, w, stride, sc, tag, train, kupd, **kw)
             y = self._buf((tag, p, "y"), (G * rows_out, cout), f32)
             nxt = self.blocks[bi + 1][0] + "bn1" if bi + 1 < len(self.blocks) else "bn1"        # (the last block feeds the final BatchNorm)
-            st2 = self._conv_bn(p + "conv2.weight", c1, p + "bn2", False, B, ho, wo, 1, y, tag, train, upd, resid=sc, next_bn=nxt, publish=True, **kw)
+            st2 = self._conv_bn(p + "conv2.weight", c1, p + "bn2", False, B, ho, wo, 1, y, tag, train, kupd, resid=sc, next_bn=nxt, publish=True, **kw)
             if save:
                 pick = (lambda st: st) if G == 1 else (lambda st: (st[0][G - 1], st[1][G - 1]))
                 ctx.blocks.append(dict(x=last(out, B * h * w), st1=pick(st1), c1=last(c1, rows_out), st2=pick(st2), raw=raw, h=h, w=w, ho=ho, wo=wo))
@@ -365,11 +393,15 @@ class WideResNet(ModuleSurface):
             stf = self._stats_bufs("bn1", C3, tag, G)
             ops.wrn_head(out, 3, None, accs["bn1"], self.p("bn1.weight"), self.p("bn1.bias"), self.eps["bn1"], SLOPE,
                          self.p("classifier.weight"), self.p("classifier.bias"), feat, logits, B, h * w, C3, self.num_classes, publish=stf,
-                         running=run, momentum=MOMENTUM, update_running=upd, stat_ranks=self.stat_ranks, passes=G)
+                         running=run, momentum=MOMENTUM, update_running=kupd, stat_ranks=self.stat_ranks, passes=G)
             stf_first = (stf[0][0], stf[1][0]) if G > 1 else None
             if G > 1:
                 stf = (stf[0][G - 1], stf[1][G - 1])
-            if upd:
+            if allg:
+                chain.append(("bn1", C3, rows * self.stat_ranks))
+                self._running_chain(chain, accs, G, tag)
+                self._nbt += G                                  # (every pass is a model() call of its own)
+            elif upd:
                 self._nbt += 1                                  # num_batches_tracked of all BatchNorms (each was visited once)
         else:
             stf = None
@@ -400,6 +432,36 @@ class WideResNet(ModuleSurface):
         if first_img is not None:
             return self.forward_features(img, save=True, update_stats=True, tag=tag, passes=passes + 1, first_img=first_img)
         return self.forward_features(img, save=True, update_stats=False, tag=tag, passes=passes)
+
+    MAX_SHARED_PASSES = 64        # (srhip_wrn_conv_bn_passes refuses more statistics groups per launch)
+
+    def forward_cat_passes(self, img, passes, tag="cat"):
+        """``passes`` model() calls on the SAME batch in training mode with no Bn_Controller (the K + 1 calls on cat(x_lb, x_ulb_w, x_ulb_s) of
+        an SRFixMatch / SRFlexMatch / SRFreeMatch / SRSoftMatch step, fixmatch.py:62-146): every pass is one BatchNorm statistics group over
+        the whole batch and every pass moves the running statistics and num_batches_tracked, in pass order.  Shared launches; more than
+        MAX_SHARED_PASSES run as chunks in pass order (the running chain continues across them).  Returns (logits [passes * B, C], feat
+        [passes * B, F], ctxs): ctxs = (ctx of pass 0, ctx of the last pass), or (ctx,) for one pass."""
+        G, M = int(passes), self.MAX_SHARED_PASSES
+        assert G >= 1
+        if G <= M:
+            lg, ft, ctx = self.forward_features(img, save=True, update_stats=True, tag=tag, passes=G, all_groups=True, keep_first=True)
+            return lg, ft, (ctx if G > 1 else (ctx,))
+        # Chunks in pass order: the first keeps pass 0, the last keeps the last pass, the ones between keep nothing -- so all of THOSE may
+        # forward through ONE buffer set (':mid'; their logits / features are fresh tensors per call).  The first chunk is forwarded with
+        # keep_first, which also fills a ctx for that chunk's own last pass: views of buffers that exist anyway, dropped here.
+        sizes = [M] * (G // M) + ([G % M] if G % M else [])
+        lgs, fts, ctx0, ctxl = [], [], None, None
+        for i, n in enumerate(sizes):
+            first, lastc = i == 0, i == len(sizes) - 1
+            lg, ft, ctx = self.forward_features(img, save=first or lastc, update_stats=True, passes=n, all_groups=True, keep_first=first,
+                                                tag=tag + (":head" if first else "" if lastc else ":mid"))
+            if first:
+                ctx0 = ctx[0]
+            if lastc:
+                ctxl = ctx[-1] if isinstance(ctx, tuple) else ctx
+            lgs.append(lg)
+            fts.append(ft)
+        return torch.cat(lgs), torch.cat(fts), (ctx0, ctxl)
 
     def forward(self, x, only_fc=False, only_feat=False, **kw):
         assert not only_fc

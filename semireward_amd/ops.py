@@ -1221,6 +1221,25 @@ def wrn_head(x, in_mode, in_stats, in_acc, gamma, beta, eps, slope, Wc, bc, feat
           int(update_running), _p(Wc), _p(bc), _p(feat), _p(logits), B, HW2, C, K, stat_ranks, int(passes), _s())
 
 
+BN_CHAIN_DESC_DTYPE = [("acc", "<u8"), ("running_mean", "<u8"), ("running_var", "<u8"), ("C", "<i4"), ("rows", "<i4")]
+
+
+def make_bn_chain_desc(entries, device):
+    """entries: (acc [groups, bn_acc_doubles(C)] fp64, running_mean, running_var, C, rows).  Returns (device table, n) for bn_running_chain."""
+    import numpy as np
+    arr = np.zeros(len(entries), dtype=BN_CHAIN_DESC_DTYPE)
+    for i, (acc, rm, rv, C, rows) in enumerate(entries):
+        assert 0 < C <= 256 and rows > 0
+        arr[i] = (_p(acc), _p(rm), _p(rv), C, rows)
+    assert arr.itemsize == 32
+    return torch.from_numpy(arr.view(np.uint8).copy()).to(device), len(entries)
+
+
+def bn_running_chain(desc, n, groups, momentum):
+    """Every statistics group of a shared-launch forward moves the running statistics, in group order (srhip_bn_running_chain)."""
+    _call("srhip_bn_running_chain", _p(desc), n, int(groups), momentum, _s())
+
+
 def bn_stats(x, eps, momentum, update_running, running_mean, running_var, out_mean, out_invstd, ws, rows, C):
     _call("srhip_bn_stats", _p(x), eps, momentum, int(update_running), _p(running_mean), _p(running_var), _p(out_mean), _p(out_invstd), _p(ws),
           rows, C, _s())
