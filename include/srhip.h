@@ -134,6 +134,13 @@ int srhip_attn_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, 
 int srhip_attn_bwd(const void* qkv, const void* out, const void* d_out, const float* lse, void* dqkv, float* delta_ws,
                    int B, int N, int H, float scale, void* stream);
 
+/* Host logic of the four entry points above and below, no launch: what a (B, N, H) launch reaches.  nkt = the key-tile instantiation
+ * (2, 8, 14, 18 or 32 tiles of 16 keys: the smallest that holds N), fwd_pair = 1 when the forward is attn_fwd_pair_kernel (N > 288),
+ * bwd_l2 = 1 when the backward reads its V / (q, dO) row fragments from L2 (N > 288), bwd_split = the backward grid's blockIdx.y extent
+ * (query / key tiles split over extra workgroups while B*H*split*2 < 128).  Any out pointer may be NULL.  SR_EINVAL exactly where the
+ * launchers refuse the shape. */
+int srhip_attn_plan(int B, int N, int H, int* nkt, int* fwd_pair, int* bwd_l2, int* bwd_split);
+
 /* Padding-aware variants for the BERT / Wav2Vec2 encoders (semilearn/nets/bert/bert.py:34 -> transformers BertSelfAttention;
  * wave2vecv2/wave2vecv2.py:44 -> Wav2Vec2Attention): key_len int32 [B] = number of valid (non-padding) keys of every sequence of a
  * right-padded batch (NULL: all N), equivalent to the additive -inf attention mask; every query row is computed.  drop_*: train-mode
@@ -143,7 +150,14 @@ int srhip_attn_bwd(const void* qkv, const void* out, const void* d_out, const fl
  * oracle/bert_ref.keep_mask restates it).  At THIS site the pairs are taken within a query row: pair = ((b*H + h)*N + q) * ceil(N / 2) +
  * (key >> 1); at every other site (srhip_gemm_nt_resid_dropout, embeddings, post-LN, pooling) pair = i >> 1 of the row-major element index i.
  * N <= 512 forward AND backward (N > 288: the forward walks two query tiles per wave through 128-key blocks, attn_fwd_pair_kernel; the V
- * fragments of the dQ pass come from L2 instead of LDS).  B*H*N*N < 2^32. */
+ * fragments of the dQ pass come from L2 instead of LDS).  B*H*N*N < 2^32.
+ * key_len contract: 1 <= key_len[b] <= N for every sequence; the kernels do not check it on the device.  A sequence without a valid key has
+ * no softmax (the whole-row forward would write NaN rows, the paired forward walks no key block), a length above N reads no further than N but
+ * is not a supported argument.  The range is the caller's to keep: the BERT engine takes key_len = the row sums of the prefix mask it is handed
+ * (srhip_mask_lengths; TokenBatch.from_dict accepts any attention_mask), so key_len <= L always holds, and key_len >= 1 is ASSUMED of the
+ * tokenizer -- every tokenised sequence holds at least [CLS] and [SEP] -- and not checked: an all-zero mask row would break the contract; the
+ * Wav2Vec2 engine passes the frame count of the clip length for every clip, 1 <= T <= the frame pitch it launches as N.  Padded rows (key_len[b] <= row < N) of K and V
+ * may hold any finite values: they never reach a result, and their dK and dV rows are written as zeros. */
 int srhip_attn_masked_fwd(const void* qkv, void* out, float* lse, const int* key_len, int B, int N, int H, float scale,
                           unsigned drop_key, unsigned drop_thresh, float drop_scale, void* stream);
 int srhip_attn_masked_bwd(const void* qkv, const void* out, const void* d_out, const float* lse, void* dqkv, float* delta_ws,

@@ -38,6 +38,7 @@ SIGNATURES = {
     "srhip_slab_reduce_f32": (I, [P, I, I, P]),
     "srhip_attn_fwd": (I, [P, P, P, I, I, I, F, P]),
     "srhip_attn_bwd": (I, [P, P, P, P, P, P, I, I, I, F, P]),
+    "srhip_attn_plan": (I, [I, I, I, P, P, P, P]),
     "srhip_layernorm_fwd": (I, [P, P, P, F, P, P, P, I, I, P]),
     "srhip_layernorm_bwd": (I, [P, P, P, P, P, P, P, P, I, I, P]),
     "srhip_layernorm_bwd_cast": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, P]),

@@ -1019,15 +1019,46 @@ int dispatch_nkt(int N, F&& f) {
   return SR_EINVAL;
 }
 
-template <bool VAR>
-int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, AttnVar av, void* stream) {
+// Every host decision of a launch in one place (also exported as srhip_attn_plan so that a test can pin which kernel and grid a shape reaches):
+// the key-tile instantiation, the forward kernel, the backward form and the backward's blockIdx.y extent.  The tuning-build overrides stay in
+// the launchers.
+constexpr bool attn_fwd_pair(int nkt) { return nkt == 32; }      // 288 < N <= 512: two query tiles per wave through 128-key blocks (attn_fwd_pair_kernel)
+constexpr bool attn_bwd_l2(int nkt) { return nkt > 18; }         // K + V + K^T images exceed the LDS: V / (q, dO) row fragments from L2 (VG / QG)
+constexpr size_t attn_fwd_smem(int nkt) { return (size_t)nkt * 16 * HD * 2 + (size_t)64 * vt_pitch(nkt * 16) * 2; }
+constexpr size_t attn_bwd_smem(int nkt) {
+  const int NP = nkt * 16;
+  const bool VG = attn_bwd_l2(nkt);
+  const size_t sm1 = (size_t)(VG ? 1 : 2) * NP * HD * 2 + (size_t)64 * vt_pitch(NP) * 2 + (size_t)2 * NP * 4;
+  const size_t sm2 = (size_t)2 * 64 * vt_pitch(NP) * 2 + (VG ? 0 : (size_t)2 * NP * HD * 2) + (size_t)2 * NP * 4;
+  return sm1 > sm2 ? sm1 : sm2;
+}
+struct AttnPlan { int nkt, fwd_pair, bwd_l2, bwd_split; };
+int attn_plan(int B, int N, int H, AttnPlan* p) {
   if (B <= 0 || N <= 0 || H <= 0 || N > 512 || (long)B * H * N * N >= (1L << 32)) return SR_EINVAL;
   return dispatch_nkt(N, [&](auto nk) -> int {
-    constexpr int NKT = decltype(nk)::value, NP = NKT * 16;
-    const size_t sm = (size_t)NP * HD * 2 + (size_t)64 * vt_pitch(NP) * 2;
-    if constexpr (NKT == 32) {                // 288 < N <= 512: two query tiles per wave through 128-key blocks (attn_fwd_pair_kernel)
+    constexpr int NKT = decltype(nk)::value;
+    if (attn_bwd_smem(NKT) > 160 * 1024) return SR_EINVAL;
+    // split query / key tiles over extra workgroups until the grid covers the chip (each split re-stages K/V or Q/dO)
+    const int nt16 = (N + 15) / 16;
+    // (measured at the reference batch, 96 (image, head) pairs x 2 roles: no split 1087 img/s, split 2 1072, split 3 1065 while the deferred
+    // rows share the chip -- every split re-stages K / V / Q / dO; alone on the chip (K = 0 regime) split 3 wins by 1 %)
+    int split = 1;
+    while (B * H * split * 2 < 128 && split * BWD_NW < nt16) ++split;
+    *p = AttnPlan{NKT, attn_fwd_pair(NKT), attn_bwd_l2(NKT), split};
+    return SR_OK;
+  });
+}
+
+template <bool VAR>
+int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, AttnVar av, void* stream) {
+  AttnPlan plan;
+  if (const int rc = attn_plan(B, N, H, &plan)) return rc;
+  return dispatch_nkt(N, [&](auto nk) -> int {
+    constexpr int NKT = decltype(nk)::value;
+    const size_t sm = attn_fwd_smem(NKT);
+    if constexpr (attn_fwd_pair(NKT)) {
       static const bool whole_row = SR_TUNE_ENV("SRHIP_ATTN_FWD_WHOLE_ROW") != nullptr;   // tuning build: the whole-row kernel at every length (A/B)
-      if (!whole_row) {
+      if (plan.fwd_pair && !whole_row) {
         auto kp = attn_fwd_pair_kernel<VAR>;
         (void)hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
         SR_LAUNCH(kp, dim3(B * H), dim3(FWD_NT), sm, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, scale, av);
@@ -1046,22 +1077,15 @@ int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int N, int H,
 template <bool VAR>
 int attn_bwd_launch(const void* qkv, const void* out, const void* d_out, const float* lse, void* dqkv, float* delta_ws, int B, int N, int H,
                     float scale, AttnVar av, void* stream) {
-  if (B <= 0 || N <= 0 || H <= 0 || N > 512 || !lse || !delta_ws || (long)B * H * N * N >= (1L << 32)) return SR_EINVAL;
+  AttnPlan plan;
+  if (!lse || !delta_ws) return SR_EINVAL;
+  if (const int rc = attn_plan(B, N, H, &plan)) return rc;
   return dispatch_nkt(N, [&](auto nk) -> int {
-    constexpr int NKT = decltype(nk)::value, NP = NKT * 16;
-    constexpr bool VG = NKT > 18;           // K + V + K^T images exceed the LDS: V fragments from L2
-    const size_t sm1 = (size_t)(VG ? 1 : 2) * NP * HD * 2 + (size_t)64 * vt_pitch(NP) * 2 + (size_t)2 * NP * 4;
-    const size_t sm2 = (size_t)2 * 64 * vt_pitch(NP) * 2 + (VG ? 0 : (size_t)2 * NP * HD * 2) + (size_t)2 * NP * 4;
-    if (sm1 > 160 * 1024 || sm2 > 160 * 1024) return SR_EINVAL;
-    auto kern = attn_bwd_kernel<NKT, VAR, VG>;
-    const size_t sm = sm1 > sm2 ? sm1 : sm2;
+    constexpr int NKT = decltype(nk)::value;
+    auto kern = attn_bwd_kernel<NKT, VAR, attn_bwd_l2(NKT)>;
+    const size_t sm = attn_bwd_smem(NKT);
     if (sm > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    // split query / key tiles over extra workgroups until the grid covers the chip (each split re-stages K/V or Q/dO)
-    const int nt16 = (N + 15) / 16;
-    // (measured at the reference batch, 96 (image, head) pairs x 2 roles: no split 1087 img/s, split 2 1072, split 3 1065 while the deferred
-    // rows share the chip -- every split re-stages K / V / Q / dO; alone on the chip (K = 0 regime) split 3 wins by 1 %)
-    int split = 1;
-    while (B * H * split * 2 < 128 && split * BWD_NW < nt16) ++split;
+    int split = plan.bwd_split;
     static const char* force = SR_TUNE_ENV("SRHIP_ATTN_BWD_SPLIT");
     if (force && atoi(force) > 0) split = atoi(force);
     SR_LAUNCH(kern, dim3(B * H, split, 2), dim3(BWD_NT), sm, (hipStream_t)stream, (const bf16_t*)qkv, (const bf16_t*)out,
@@ -1078,6 +1102,15 @@ extern "C" int srhip_attn_debug(long long* out_host, int n) {
   return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(srhip_attn_dbg), (size_t)n * sizeof(long long)) == hipSuccess ? SR_OK : SR_EINVAL;
 }
 #endif
+extern "C" int srhip_attn_plan(int B, int N, int H, int* nkt, int* fwd_pair, int* bwd_l2, int* bwd_split) {
+  AttnPlan plan;
+  if (const int rc = attn_plan(B, N, H, &plan)) return rc;
+  if (nkt) *nkt = plan.nkt;
+  if (fwd_pair) *fwd_pair = plan.fwd_pair;
+  if (bwd_l2) *bwd_l2 = plan.bwd_l2;
+  if (bwd_split) *bwd_split = plan.bwd_split;
+  return SR_OK;
+}
 extern "C" int srhip_attn_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, void* stream) {
   return attn_fwd_launch<false>(qkv, out, lse, B, N, H, scale, AttnVar{nullptr, 0u, 0u, 1.0f}, stream);
 }

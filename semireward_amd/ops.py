@@ -1,5 +1,6 @@
 """Torch-tensor front end of the C ABI (include/srhip.h).  Torch is plumbing only: it owns device
 memory and the stream; every op below is a hand-written HIP kernel in libsrhip.so.  No fallbacks."""
+import collections
 import ctypes
 import os
 
@@ -501,6 +502,19 @@ def attn_block_fused(xn, Wqkv, bqkv, out, B, N, D, H, scale, qkv_extra=None, out
                               2.0 * M * D + 2.0 * M * D + 2.0 * 3 * D * D)
         return
     _call("srhip_attn_block_fused", _p(xn), _p(Wqkv), _p(bqkv), _p(qkv_extra), _p(out), _p(out_scale), B, N, D, H, scale, _s())
+
+
+AttnPlan = collections.namedtuple("AttnPlan", "nkt fwd_pair bwd_l2 bwd_split")
+
+
+def attn_plan(B, N, H):
+    """What an attention launch of this shape reaches (host logic, no launch; srhip_attn_plan): the key-tile instantiation, whether the
+    forward is the paired kernel, whether the backward takes the L2 form, and the backward grid's blockIdx.y extent."""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    rc = int(_lib.lib().srhip_attn_plan(B, N, H, *[ctypes.addressof(x) for x in v]))
+    if rc != 0:
+        _lib.check(rc, "srhip_attn_plan")
+    return AttnPlan(v[0].value, bool(v[1].value), bool(v[2].value), v[3].value)
 
 
 def attn_fwd(qkv, out, lse, B, N, H, scale):

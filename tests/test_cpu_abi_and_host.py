@@ -42,6 +42,12 @@ def test_invalid_arguments_return_error_codes_without_gpu():
     lib = _lib.lib()
     assert lib.srhip_gemm_nt(0, None, 64, None, 64, None, 64, 16, 16, 100, None, None, 0, None, None, 0, 1.0, 0.0, None) == -1
     assert lib.srhip_attn_fwd(None, None, None, 1, 1000, 6, 0.125, None) == -1
+    # srhip_attn_plan refuses what the attention launchers refuse: N > 512, a zero extent, B*H*N*N >= 2^32 (the dropout row index)
+    for B, N, H in [(1, 513, 6), (0, 257, 6), (1, 0, 6), (1, 257, 0), (1366, 512, 12)]:
+        assert lib.srhip_attn_plan(B, N, H, None, None, None, None) == -1, (B, N, H)
+        assert lib.srhip_attn_fwd(None, None, None, B, N, H, 0.125, None) == -1, (B, N, H)
+        assert lib.srhip_attn_bwd(0x10000, 0x10000, 0x10000, 0x10000, 0x10000, 0x10000, B, N, H, 0.125, None) == -1, (B, N, H)
+    assert lib.srhip_attn_plan(1365, 512, 12, None, None, None, None) == 0
     assert lib.srhip_layernorm_fwd(None, None, None, 1e-6, None, None, None, 4, 100, None) == -1
     assert lib.srhip_rewarder_fwd(None, None, None, None, None, None, 2, 8, 384, 100, 1, None) == -1     # save needs G == 1
     # audio front end (w2v_ops.hip): the guards reject before any launch.  The pointers are 16-byte aligned host addresses that are never
@@ -463,6 +469,27 @@ def test_gemm_tile_dispatch_is_pinned_per_shape_family(monkeypatch):
     finally:
         ops.gemm_small_max_grid(ops.GEMM_SMALL_ALONE)
     assert {k: ops.gemm_nt_plan(k[1], k[2], k[3], k[4], beta=1.0 if k[1] == ops.EPI_F32 else 0.0) for k in want} == want
+
+
+def test_attention_dispatch_is_pinned_per_shape_family():
+    """srhip_attn_plan (host logic of the four attention entry points, no launch): the key-tile instantiation, the forward kernel, the backward
+    form and the backward grid of the shapes the legs launch, and both edges of every instantiation."""
+    from semireward_amd import ops
+    want = {   # (B, N, H): (nkt, paired forward, L2 backward, blockIdx.y extent of the backward)
+        (16, 257, 6): (18, False, False, 1),       # ViT-S/2 gradient rows: 96 (image, head) pairs
+        (16, 197, 6): (14, False, False, 1),       # ViT-S/16
+        (1, 257, 6): (18, False, False, 3),
+        (8, 512, 12): (32, True, True, 1),         # BERT legs
+        (2, 512, 12): (32, True, True, 3),
+        (4, 199, 12): (14, False, False, 2),       # Wav2Vec2 frames
+    }
+    for n, nkt in ((1, 2), (32, 2), (33, 8), (128, 8), (129, 14), (224, 14), (225, 18), (288, 18), (289, 32), (512, 32)):
+        p = ops.attn_plan(1, n, 1)
+        assert p.nkt == nkt and p.fwd_pair == (n > 288) and p.bwd_l2 == (n > 288), (n, p)
+        assert p.bwd_split == min(-(-((n + 15) // 16) // 8), 64), (n, p)       # B*H = 1: split until 8 * split tiles cover the sequence
+    assert {k: tuple(ops.attn_plan(*k)) for k in want} == want
+    with pytest.raises(RuntimeError):
+        ops.attn_plan(1, 513, 1)
 
 
 def test_weight_gradient_table_of_the_persistent_kernel_is_balanced_on_the_host():
