@@ -242,6 +242,19 @@ int srhip_mlp_fused_proj_strided(const float* x, float* x_out, const void* ao, c
                                  int ao_scaled, const float* ln_gamma, const float* ln_beta, float eps, const void* W1, const float* b1,
                                  const void* W2, const float* b2, const float* row_scale2, int rows_per_sample, void* ln_next,
                                  const float* next_gamma, const float* next_beta, int M, int D, int Hd, int row_pitch, void* stream);
+/* srhip_mlp_fused_proj whose rows follow one block's row of a DropPath plan (srhip_vit_droppath_plan): plan_row int32 [1 + B], plan_row[0] =
+ * n_mlp, plan_row[1 ..] = a permutation of the B samples with the n_mlp samples whose row_scale2 is not 0 first.  Virtual row v of the launch
+ * is row v % rows_per_sample of sample plan_row[1 + v / rows_per_sample] in x, x_out, ao and ln_next, and takes that sample's two factors.
+ * A 128-row tile that starts below virtual row n_mlp * rows_per_sample runs what srhip_mlp_fused_proj runs; the others hold only rows whose
+ * MLP branch is dropped (row_scale2 == 0, vit.py:165: x1 + 0 * (...) = x1) and stop after the projection: x_out = x1, ln_next = LayerNorm(x1).
+ * Every row is still written, M and the grid do not depend on device data, and a row's values do not depend on the tile that carries it:
+ * bit for bit srhip_mlp_fused_proj's, except that a skipped branch adds nothing where that launch adds products of +-0 (the sign of an
+ * exactly-zero element may differ; an Inf / NaN inside a dropped branch does not reach the row).  row_scale2 must be given.
+ * SR_EINVAL: plan_row NULL, B <= 0, M != B * rows_per_sample, and whatever srhip_mlp_fused_proj refuses. */
+int srhip_mlp_fused_proj_planned(const float* x, float* x_out, const void* ao, const void* Wp, const float* bp, const float* row_scale1,
+                                 int ao_scaled, const float* ln_gamma, const float* ln_beta, float eps, const void* W1, const float* b1,
+                                 const void* W2, const float* b2, const float* row_scale2, int rows_per_sample, void* ln_next,
+                                 const float* next_gamma, const float* next_beta, int M, int D, int Hd, const int* plan_row, int B, void* stream);
 
 /* Fused qkv projection + attention of a ViT block for rows without a backward: ao = softmax(q k^T * scale) v with [q | k | v] = xn Wqkv^T +
  * bqkv -- Attention.forward up to the output projection (semilearn/nets/vit/vit.py:93-104) on the norm1 output (:163) in ONE launch, one
@@ -251,7 +264,8 @@ int srhip_mlp_fused_proj_strided(const float* x, float* x_out, const void* ao, c
  * is an argument error.  N = 257 = 16 token tiles + one token: qkv_extra bf16 [B, 3D] = q | k | v of token 256 of every image (one
  * srhip_gemm_nt over the B rows xn_bf16 + 256 * D with lda = N * D) must be given; ignored for N = 197.
  * out_scale fp32 [B] or NULL: factor on every output row of image b, applied before the bf16 rounding -- the DropPath factor of the attention
- * branch (vit.py:163) when the consumer is srhip_mlp_fused_proj(ao_scaled = 1). */
+ * branch (vit.py:163) when the consumer is srhip_mlp_fused_proj(ao_scaled = 1).  An image whose factor is exactly 0 (a dropped branch) gets
+ * +0 in all of its output rows without its projections or its softmax being computed. */
 int srhip_attn_block_supported(int N, int D, int H);
 int srhip_attn_block_fused(const void* xn_bf16, const void* Wqkv, const float* bqkv, const void* qkv_extra, void* out, const float* out_scale,
                            int B, int N, int D, int H, float scale, void* stream);
@@ -387,6 +401,12 @@ int srhip_droppath_fill(float* out, const float* probs, int depth, int B, unsign
  * takes a contiguous column slice -- instead of an index_select per train on the step's critical path. */
 int srhip_droppath_fill_cols(float* out, const float* probs, const long long* cols, int depth, int B, int n_cols, unsigned long long seed,
                              void* stream);
+/* DropPath plan of one forward, built on the device from the table its launches read: dp[l * stride_block + j * stride_branch + b] (strides
+ * in elements: a contiguous [depth, 2, B] table or a column slice of a wider one).  plan int32 [depth, 1 + B]: plan[l][0] = n_mlp, the number
+ * of samples whose MLP factor dp[l, 1, b] is not 0; plan[l][1 .. B] = a stable partition of 0 .. B-1, those samples first in ascending
+ * order, then the others in ascending order (srhip_mlp_fused_proj_planned takes row l).  Reads device memory only, so it replays inside a
+ * captured step.  One workgroup per block, any B. */
+int srhip_vit_droppath_plan(const float* dp, long long stride_block, long long stride_branch, int depth, int B, int* plan, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Pass-prefix sharing of ViT inference rows (share_pass_prefixes, csrc/pass_tree.hip).  The K + 1 passes of a step forward the same images

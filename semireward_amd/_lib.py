@@ -50,6 +50,7 @@ SIGNATURES = {
     "srhip_gelu_eval": (I, [P, P, P, I, P]),
     "srhip_mlp_fused_proj": (I, [P, P, P, P, P, P, I, P, P, F, P, P, P, P, P, I, P, P, P, I, I, I, P]),
     "srhip_mlp_fused_proj_strided": (I, [P, P, P, P, P, P, I, P, P, F, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
+    "srhip_mlp_fused_proj_planned": (I, [P, P, P, P, P, P, I, P, P, F, P, P, P, P, P, I, P, P, P, I, I, I, P, I, P]),
     "srhip_adam_bias_corrections": (I, [F, F, I, P]),
     "srhip_adamw_flat_dyn": (I, [P, P, P, P, P, P, P, I, P, P, P, F, F, F, Dbl, F, P, I, P]),
     "srhip_adam_flat_dyn": (I, [P, P, P, P, L, F, F, F, F, P, P]),
@@ -80,6 +81,7 @@ SIGNATURES = {
     "srhip_transpose_batched": (I, [P, I, I, P]),
     "srhip_cast_f32_bf16": (I, [P, P, L, P]),
     "srhip_droppath_fill": (I, [P, P, I, I, c_ulonglong, P]),
+    "srhip_vit_droppath_plan": (I, [P, c_longlong, c_longlong, I, I, P, P]),
     "srhip_droppath_fill_cols": (I, [P, P, P, I, I, I, c_ulonglong, P]),
     "srhip_row_max": (I, [P, I, P, P, P, I, I, P]),
     "srhip_row_max_strided": (I, [P, I, P, P, P, I, I, I, c_longlong, P]),

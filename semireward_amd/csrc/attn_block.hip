@@ -113,7 +113,7 @@ struct AbArgs {
   const float* bqkv;
   const bf16_t* W;         // [1152, 384] bf16: q | k | v rows, head-major inside each third (vit.py:93-98)
   bf16_t* out;             // [B * N, 384] attention output, heads concatenated (vit.py:104 transpose + reshape)
-  const float* osc;        // [B] factor on the image's output rows (DropPath of the branch, vit.py:163), applied before the bf16 rounding; or NULL
+  const float* osc;        // [B] factor on the image's output rows (DropPath of the branch, vit.py:163), applied before the bf16 rounding; or NULL.  A factor of exactly 0: +0 rows, nothing computed
   float scale;
   int B;
 };
@@ -127,6 +127,19 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(AbArgs a) {
   constexpr bool EXTRA = NQT == 17;                  // N = 257: tile 16 holds exactly one token
   static_assert(NQT <= 16 || (EXTRA && N == 257), "two token tiles per wave (+ one extra token)");
   constexpr int NKT_LO = (N - 1) / 16;               // key tiles below this index are complete
+  // A dropped branch (DropPath factor exactly 0, vit.py:163): every output row of the image is 0 whatever the projections and the softmax give,
+  // so the workgroup writes +0 to its slice of out (the consumer still reads it: stale bytes could be NaN) and leaves before any DMA, LDS use
+  // or barrier.  Workgroup-uniform: one scalar per image.  (In front of everything else, with names of its own: placed behind the index
+  // arithmetic below it cost the main path a register and six SGPRs.)
+  if (a.osc && a.osc[blockIdx.x] == 0.0f) {
+    const int hpw0 = NH / gridDim.y, cw = hpw0 * (HD / 8);          // 16-byte chunks of this workgroup's columns per row
+    bf16_t* o = a.out + (size_t)blockIdx.x * N * DM + blockIdx.y * hpw0 * HD;
+    for (int i = threadIdx.x; i < N * cw; i += 512) {
+      const int r = i / cw, c = i - r * cw;
+      *reinterpret_cast<u32x4_t*>(o + (size_t)r * DM + 8 * c) = u32x4_t{0u, 0u, 0u, 0u};
+    }
+    return;
+  }
   extern __shared__ __attribute__((aligned(16))) bf16_t sm[];
   bf16_t* ring = sm;                                 // [NS][64][64]
   bf16_t* Ks = ring + NS * ST_EL;                    // [NP][64]   chunk c of row r at c ^ ((r >> 1) & 7)
@@ -142,7 +155,6 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(AbArgs a) {
   // re-reads the image's normalised rows: 197 KB from L2) so that its latency is that of 3 or 2 heads instead of 6
   const int hpw = NH / gridDim.y, hbeg = blockIdx.y * hpw, hend = hbeg + hpw;
   const size_t row0 = (size_t)img * N;
-
   // ---- ring producer: LDS row rho = 8 wave + (lane >> 3), chunk position pc = lane & 7 holds source chunk pc ^ ((rho >> 1) & 7) of
   // feature row perm(rho) (K, Q: inside every 32-block, LDS rows 0-15 = features 8 (i >> 2) + (i & 3), rows 16-31 = the same + 4) or rho (V)
   const int rho = 8 * wave + (lane >> 3);

@@ -505,6 +505,40 @@ __global__ void droppath_fill_kernel(float* __restrict__ out, const float* __res
   out[o] = (p <= 0.f) ? 1.0f : (u < keep ? 1.0f / keep : 0.0f);
 }
 
+// DropPath plan of one forward, from the table the launches read (device memory only: replays inside a captured step).  Workgroup l handles
+// block l: plan[l][0] = the number of samples whose MLP factor dp[l, 1, b] is not 0, plan[l][1 ..] = a stable partition of 0 .. B-1, those samples
+// first (ascending), the dropped ones behind them (ascending).  Chunks of 256 samples: ballot + popcount inside a wave, the four wave counts
+// through LDS; a dropped sample's place follows from the kept count in front of it (b - kept_before(b) dropped ones precede it).
+__global__ __launch_bounds__(256) void droppath_plan_kernel(const float* __restrict__ dp, long long stride_block, long long stride_branch, int B,
+                                                            int* __restrict__ plan) {
+  __shared__ int wcnt[2][4];
+  const float* f = dp + (long long)blockIdx.x * stride_block + stride_branch;
+  int* row = plan + (size_t)blockIdx.x * (1 + B);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int n_keep = 0;
+  for (int b0 = 0, it = 0; b0 < B; b0 += 256, ++it) {          // pass 1: the count (uniform trip count: every thread reaches every barrier)
+    const int b = b0 + tid;
+    const unsigned long long m = __ballot(b < B && f[b] != 0.f);
+    if (lane == 0) wcnt[it & 1][w] = __popcll(m);
+    __syncthreads();                                            // (two buffers: the next round's writes cannot pass this round's reads)
+    n_keep += wcnt[it & 1][0] + wcnt[it & 1][1] + wcnt[it & 1][2] + wcnt[it & 1][3];
+  }
+  __syncthreads();
+  if (tid == 0) row[0] = n_keep;
+  int before = 0;                                               // kept samples below b0
+  for (int b0 = 0, it = 0; b0 < B; b0 += 256, ++it) {          // pass 2: the places
+    const int b = b0 + tid;
+    const bool keep = b < B && f[b] != 0.f;
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wcnt[it & 1][w] = __popcll(m);
+    __syncthreads();
+    int kb = before + __popcll(m & ((1ull << lane) - 1ull));    // kept samples below b
+    for (int i = 0; i < w; ++i) kb += wcnt[it & 1][i];
+    if (b < B) row[1 + (keep ? kb : n_keep + (b - kb))] = b;
+    before += wcnt[it & 1][0] + wcnt[it & 1][1] + wcnt[it & 1][2] + wcnt[it & 1][3];
+  }
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -779,6 +813,14 @@ extern "C" int srhip_droppath_fill_cols_dyn(float* out, const float* probs, cons
   if (depth <= 0 || B <= 0 || n_cols <= 0 || !seed_dev) return SR_EINVAL;
   SR_LAUNCH(droppath_fill_kernel, dim3(cdiv((long)depth * 2 * n_cols, 256)), dim3(256), 0, (hipStream_t)stream, out, probs, depth, B, seed_offset,
                      cols, cols ? n_cols : B, seed_dev);
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+// plan int32 [depth, 1 + B] of the table dp[l * stride_block + j * stride_branch + b] (a column slice of a wider table is fine): see the kernel
+extern "C" int srhip_vit_droppath_plan(const float* dp, long long stride_block, long long stride_branch, int depth, int B, int* plan,
+                                       void* stream) {
+  if (!dp || !plan || depth <= 0 || B <= 0 || stride_block < 0 || stride_branch < 0) return SR_EINVAL;
+  SR_LAUNCH(droppath_plan_kernel, dim3(depth), dim3(256), 0, (hipStream_t)stream, dp, stride_block, stride_branch, B, plan);
   SR_CHECK_LAUNCH();
   return SR_OK;
 }

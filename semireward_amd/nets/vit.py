@@ -15,6 +15,7 @@ Data layout in HBM (B images, N tokens, D channels, M = B*N rows):
   weights                   bf16 [out, in]   (+ transposed bf16 copies for the dX products)
 """
 import math
+import os
 import types
 
 import numpy as np
@@ -69,6 +70,11 @@ _FUSED_PROJ = True         # attention projection + residual inside the fused ML
 _FUSED_NEXT_LN = True      # ... which then also writes the next block's norm1 output
 # the head reads one row per image (the class token): behind the LAST block's attention the fused proj + MLP launch runs those rows only
 _LAST_BLOCK_CLASS_ROWS = True
+# stochastic depth skips a dropped branch: the fused attention launch leaves an image whose factor is 0 before its first weight tile
+# (srhip_attn_block_fused), and the fused proj + MLP launch takes its rows through a per-forward plan built on the device that sends the
+# images whose MLP branch is dropped to tiles that stop after the projection (srhip_vit_droppath_plan, srhip_mlp_fused_proj_planned).
+# SRHIP_SKIP_DROPPED=0: the dense launch (the attention early exit is part of the kernel either way)
+_SKIP_DROPPED_BRANCHES = os.environ.get("SRHIP_SKIP_DROPPED", "1") != "0"
 # the fused kernel owns a CU per 128-row tile for ~90 us whatever the launch size: below ~half a chip of tiles (the 8 inference images of the
 # pre-start_timing regime = 17 tiles) LayerNorm + two 64x64-tiled GEMMs spread over all CUs are faster
 _FUSED_MLP_MIN_ROWS = 16384
@@ -286,6 +292,11 @@ class VisionTransformer(ModuleSurface):
         scale = 64 ** -0.5
         dst0, dst1 = (droppath.stride(0), droppath.stride(1)) if droppath is not None else (0, 0)      # (a column range of the step's table: strided rows)
         ln_ready = False           # the previous block's fused launch already wrote this block's norm1 output
+        plan = None
+        if _SKIP_DROPPED_BRANCHES and droppath is not None and tree is None and fused_attn and fused_mlp and _FUSED_PROJ:
+            # one plan per forward, from the table itself (device memory: nothing here depends on the host knowing the draws)
+            plan = self._buf(tag + "dpplan", (cfg.depth, 1 + B), torch.int32)
+            ops.vit_droppath_plan(droppath, cfg.depth, B, plan)
         for i in range(cfg.depth):
             b = "blocks.%d." % i
             if tree is not None:
@@ -338,7 +349,8 @@ class VisionTransformer(ModuleSurface):
                                    P(b + "norm2.bias"), cfg.eps, P(b + "mlp.fc1.weight", wb), P(b + "mlp.fc1.bias"),
                                    P(b + "mlp.fc2.weight", wb), P(b + "mlp.fc2.bias"), s2, rps, rows, D, Hd,
                                    ln_next=ln if ln_ready else None, next_gamma=P(nb + "norm1.weight") if ln_ready else None,
-                                   next_beta=P(nb + "norm1.bias") if ln_ready else None, ao_scaled=ao_scaled, row_pitch=pitch)
+                                   next_beta=P(nb + "norm1.bias") if ln_ready else None, ao_scaled=ao_scaled, row_pitch=pitch,
+                                   plan_row=ops.RawRows(plan, i * (1 + B)) if (plan is not None and not class_rows) else None)
             else:
                 ops.gemm_nt(ops.EPI_RESID_F32, ao, P(b + "attn.proj.weight", wb), x, M, D, D, bias=P(b + "attn.proj.bias"),
                             row_scale=s1, rows_per_sample=N, **gp)

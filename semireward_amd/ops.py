@@ -579,11 +579,14 @@ def mlp_fused(x, gamma, beta, eps, W1, b1, W2, b2, row_scale, rows_per_sample, M
 
 
 def mlp_fused_proj(x, ao, Wp, bp, row_scale1, gamma, beta, eps, W1, b1, W2, b2, row_scale2, rows_per_sample, M, D, Hd, x_out=None,
-                   ln_next=None, next_gamma=None, next_beta=None, ao_scaled=False, row_pitch=None):
+                   ln_next=None, next_gamma=None, next_beta=None, ao_scaled=False, row_pitch=None, plan_row=None):
     """x_out (default: x, in place) = x1 + row_scale2 * (fc2(gelu(fc1(LN(x1)))) + b2) with x1 = x + row_scale1 * (ao Wp^T + bp): the attention
     projection, both residuals and the MLP half of a block in ONE launch (rows without a backward).  ln_next (bf16 [M, D]): also
     LayerNorm(x_out) with the next block's norm1 affine.  ao_scaled: ao already carries row_scale1 (attn_block_fused out_scale).
-    row_pitch (elements): the M rows lie that far apart in x, x_out and ao (srhip_mlp_fused_proj_strided); rows in between are untouched."""
+    row_pitch (elements): the M rows lie that far apart in x, x_out and ao (srhip_mlp_fused_proj_strided); rows in between are untouched.
+    plan_row (int32 [1 + M / rows_per_sample], one block's row of vit_droppath_plan): srhip_mlp_fused_proj_planned -- the samples whose MLP
+    branch is dropped go to the tiles at the end of the launch, which stop after the projection."""
+    assert row_pitch is None or plan_row is None
     args = (_p(x), _p(x_out if x_out is not None else x), _p(ao), _p(Wp), _p(bp), _p(row_scale1), int(bool(ao_scaled)), _p(gamma), _p(beta), eps,
             _p(W1), _p(b1),
             _p(W2), _p(b2), _p(row_scale2), rows_per_sample, _p(ln_next), _p(next_gamma), _p(next_beta), M, D, Hd)
@@ -595,7 +598,14 @@ def mlp_fused_proj(x, ao, Wp, bp, row_scale1, gamma, beta, eps, W1, b1, W2, b2, 
             _PROFILE.timed("srhip_mlp_fused_proj_strided", (*args, int(row_pitch), _s(),), 4.0 * M * D * Hd + 2.0 * M * D * D,
                            "mlp_fused_kernel<384, 0, 4, true, 1> class rows", nbytes)
             return
+        if plan_row is not None:        # the same record as the dense launch it stands for, with that launch's nominal (reference) work
+            _PROFILE.timed("srhip_mlp_fused_proj_planned", (*args, _p(plan_row), M // rows_per_sample, _s(),), 4.0 * M * D * Hd + 2.0 * M * D * D,
+                           "mlp_fused_kernel<384, 0, 4, true, 1>", nbytes)
+            return
         _PROFILE.timed("srhip_mlp_fused_proj", (*args, _s(),), 4.0 * M * D * Hd + 2.0 * M * D * D, "mlp_fused_kernel<384, 0, 4, true, 1>", nbytes)
+        return
+    if plan_row is not None:
+        _call("srhip_mlp_fused_proj_planned", *args, _p(plan_row), M // rows_per_sample, _s())
         return
     if row_pitch is not None:
         _call("srhip_mlp_fused_proj_strided", *args, int(row_pitch), _s())
@@ -785,6 +795,15 @@ def transpose_batched(desc, n, total_tiles):
 
 def cast_f32_bf16(x, out, n):
     _call("srhip_cast_f32_bf16", _p(x), _p(out), n, _s())
+
+
+def vit_droppath_plan(dp, depth, B, plan):
+    """plan int32 [depth, 1 + B] of the DropPath table dp fp32 [depth, 2, B] (any strides over the first two dimensions, dense columns): per
+    block the number of samples that keep the MLP branch, then those samples and the dropped ones, each in ascending order."""
+    if _CHECK_ARGS:
+        assert dp.is_cuda and dp.dim() == 3 and dp.stride(2) == 1 and dp.shape[0] >= depth and dp.shape[1] == 2 and dp.shape[2] >= B and plan.dtype == torch.int32 and plan.is_contiguous()
+        assert plan.numel() == depth * (1 + B)
+    _call("srhip_vit_droppath_plan", dp.data_ptr(), dp.stride(0), dp.stride(1), depth, B, _p(plan), _s())     # (a strided view: no _p)
 
 
 def droppath_fill(out, probs, depth, B, seed, cols=None, seed_dev=None):
