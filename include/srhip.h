@@ -889,6 +889,11 @@ int srhip_wrn_conv_supported(int Cin, int Cout, int ksize);
  * for wrn_conv_tile_kernel<NT, PG> (input block in LDS), 10 NT + KS for wrn_conv_kernel<NT, KS>; 0 before the first call.  bench.py names the
  * kernel of the WideResNet leg's roofline object with it. */
 int srhip_wrn_conv_last_plan(void);
+/* The host decisions of srhip_wrn_conv_bn[_passes] for a shape, without a launch (the launcher takes its decisions from the same function):
+ * *kernel in the code of srhip_wrn_conv_last_plan, *grid_x = gridDim.x (gridDim.y = Cout / (16 NT), gridDim.z = passes), *rounds = the direct
+ * kernel's grid-stride loop count (1 for the tile kernel).  Kpad is taken as K = Cin k k rounded up to 32.  Any out pointer may be NULL.
+ * SR_EINVAL where the launcher refuses the shape. */
+int srhip_wrn_conv_plan(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int passes, int* kernel, int* grid_x, int* rounds);
 long long srhip_bn_acc_doubles(int C);
 int srhip_wrn_conv_bn(const float* xin, int in_mode, const float* in_mean, const float* in_isd, const double* in_acc, const float* in_gamma,
                       const float* in_beta, float in_eps, float slope, float* pub_mean, float* pub_invstd, float* running_mean,

@@ -641,14 +641,95 @@ extern "C" int srhip_wrn_conv_bn(const float* xin, int in_mode, const float* in_
 static int g_last_conv_plan = 0;
 extern "C" int srhip_wrn_conv_last_plan() { return g_last_conv_plan; }
 
+namespace {
+
+// The launcher's host decisions -- the ONE spelling of them: srhip_wrn_conv_bn_passes launches what conv_plan says, srhip_wrn_conv_plan reports it.
+struct ConvPlan {
+  int kernel;                  // 100 + 10 NT + PG (wrn_conv_tile_kernel) | 10 NT + KS (wrn_conv_kernel)
+  int NT, gy, PG, KS;          // PG: tile kernel only; KS: direct kernel only (0 otherwise)
+  int grid_x, rounds;          // rounds: the direct kernel's grid-stride loop count (1 for the tile kernel)
+  int Ho, Wo, npix, ntiles;
+  int TW, TH, IW, IH, tiles_x, tiles_y, ipw;
+  size_t smem;
+};
+
+// Kpad < 0: K = Cin k k rounded up to 32, as the callers of conv_weight_prep pad it
+int conv_plan(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int Kpad, int passes, ConvPlan& p) {
+  if (B <= 0 || H <= 0 || W <= 0 || stride <= 0 || !srhip_wrn_conv_supported(Cin, Cout, ksize) || passes <= 0 || passes > 64) return SR_EINVAL;
+  if (Kpad < 0) Kpad = (Cin * ksize * ksize + 31) / 32 * 32;
+  if (Kpad < Cin * ksize * ksize || (Kpad % 32)) return SR_EINVAL;
+  const int pad = ksize >> 1;
+  p.Ho = (H + 2 * pad - ksize) / stride + 1; p.Wo = (W + 2 * pad - ksize) / stride + 1;
+  p.npix = B * p.Ho * p.Wo; p.ntiles = cdiv(p.npix, 16);
+  const int NT = Cout >= 64 ? 4 : Cout / 16;                       // 16 -> 1, 32 -> 2, >= 64 -> 4
+  const int gy = Cout / (NT * 16), nks = Kpad / 32;
+  p.NT = NT; p.gy = gy; p.PG = 0; p.KS = 0; p.rounds = 1;
+  p.TW = p.TH = p.IW = p.IH = p.tiles_x = p.tiles_y = 0; p.ipw = 1; p.smem = 0;
+  // layers with >= 16 output pixels per row and whole 128 / 256-pixel blocks: the input block in LDS (wrn_conv_tile_kernel)
+  static const bool no_tile = SR_TUNE_ENV("SRHIP_CONV_NO_TILE") != nullptr;
+  if (!no_tile && ((p.Wo >= 16 && (p.Wo % 16) == 0) || (p.Wo == 8 && p.Ho == 8)) && NT >= 2 && Cin % 4 == 0) {
+    const int TW = (p.Wo % 32) == 0 ? 32 : (p.Wo == 8 ? 8 : 16);
+    // 128 pixels per workgroup (PG = 2); 256 (PG = 4: every filter fragment feeds four MFMAs) when the launch still has >= 4 workgroups per
+    // CU and the input block stays within 64 KB (two workgroups per CU)
+    auto geom = [&](int PG_) {
+      p.ipw = p.Wo == 8 ? PG_ : 1;
+      p.TW = TW; p.TH = 64 * PG_ / (TW * p.ipw); p.IW = (TW - 1) * stride + ksize; p.IH = (p.TH - 1) * stride + ksize;
+      p.tiles_x = p.Wo / TW; p.tiles_y = p.Ho / p.TH;
+      return (size_t)p.ipw * p.IH * p.IW * (Cin + 8) * sizeof(bf16_t);
+    };
+    int PG = 4;
+    size_t smem = geom(4);
+    if ((long)B * passes * p.Ho * p.Wo / 256 * gy < 1024 || p.Ho % p.TH != 0 || smem > 64 * 1024) { PG = 2; smem = geom(2); }
+    if (p.Wo == 8) {                                                 // the 8 x 8 stage: whole images, two per workgroup when the batch is even
+      PG = (B % 2 == 0) ? 2 : 1;
+      smem = geom(PG);
+      if (smem > 64 * 1024 && PG == 2) { PG = 1; smem = geom(1); }   // (the stride-2 layer into this stage: 17 x 17 input pixels per image)
+    }
+    if (p.Ho % p.TH == 0 && smem <= 64 * 1024) {
+      p.PG = PG; p.smem = smem;
+      p.grid_x = B / p.ipw * p.tiles_x * p.tiles_y;
+      p.kernel = 100 + 10 * (NT == 4 ? 4 : 2) + PG;
+      return SR_OK;
+    }
+  }
+  // <= 512 workgroups (tools/wrn_conv_bench.py: 1024 cost +2.6 us with the statistics prologue / epilogue per workgroup); the waves of a
+  // workgroup split K (2 or 4 ways) until the launch has ~2048 waves, as long as a wave keeps >= 4 k steps
+  static const int env_ks = SR_TUNE_ENV("SRHIP_CONV_KSPLIT") ? atoi(SR_TUNE_ENV("SRHIP_CONV_KSPLIT")) : 0;          // tuning: force 1 / 2 / 4
+  static const int env_maxwg = SR_TUNE_ENV("SRHIP_CONV_MAXWG") ? atoi(SR_TUNE_ENV("SRHIP_CONV_MAXWG")) : 512;
+  int KS = 1;
+  while (KS < 4 && (long)p.ntiles * passes * gy * KS * 2 <= 2048 && nks / (KS * 2) >= 4) KS *= 2;
+  if (env_ks == 1 || env_ks == 2 || env_ks == 4) KS = env_ks;
+  // workgroups per pass: the launch as a whole stays at <= env_maxwg workgroups (two rounds of the chip) however many passes share it --
+  // every workgroup pays the statistics prologue / epilogue once and then walks more pixel tiles
+  int gx = cdiv(p.ntiles, 4 / KS);
+  const int cap = env_maxwg * (passes > 1 ? 2 : 1) / (gy * passes);
+  if (gx > cap) gx = cap;
+  if (gx < 1) gx = 1;
+  p.KS = KS; p.grid_x = gx;
+  p.rounds = cdiv(p.ntiles, gx * (4 / KS));                        // wrn_conv_kernel's `rounds`
+  p.kernel = 10 * NT + KS;
+  return SR_OK;
+}
+
+}  // namespace
+
+extern "C" int srhip_wrn_conv_plan(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int passes, int* kernel, int* grid_x, int* rounds) {
+  ConvPlan p;
+  const int rc = conv_plan(B, H, W, Cin, Cout, ksize, stride, -1, passes, p);
+  if (rc != SR_OK) return rc;
+  if (kernel) *kernel = p.kernel;
+  if (grid_x) *grid_x = p.grid_x;
+  if (rounds) *rounds = p.rounds;
+  return SR_OK;
+}
+
 extern "C" int srhip_wrn_conv_bn_passes(const float* xin, int in_mode, const float* in_mean, const float* in_isd, const double* in_acc,
                                         const float* in_gamma, const float* in_beta, float in_eps, float slope, float* pub_mean, float* pub_invstd,
                                         float* running_mean, float* running_var, float momentum, int update_running, const void* Wb,
                                         const float* resid, float* y, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int Kpad,
                                         double* acc_out, int stat_ranks, int passes, void* stream) {
-  if (!xin || !Wb || !y || B <= 0 || H <= 0 || W <= 0 || stride <= 0 || !srhip_wrn_conv_supported(Cin, Cout, ksize) ||
-      Kpad < Cin * ksize * ksize || (Kpad % 32) || in_mode < 0 || in_mode > 3 || passes <= 0 || passes > 64)
-    return SR_EINVAL;
+  ConvPlan p;
+  if (!xin || !Wb || !y || in_mode < 0 || in_mode > 3 || Kpad < 0 || conv_plan(B, H, W, Cin, Cout, ksize, stride, Kpad, passes, p) != SR_OK) return SR_EINVAL;
   if (passes > 1 && (in_mode == 0 || in_mode == 1)) return SR_EINVAL;     // statistics handed in are one group's: passes fold their own (3) or read raw (2)
   if ((in_mode == 0 || in_mode == 1) && (!in_mean || !in_isd)) return SR_EINVAL;
   if (in_mode != 2 && (!in_gamma || !in_beta)) return SR_EINVAL;
@@ -664,79 +745,46 @@ extern "C" int srhip_wrn_conv_bn_passes(const float* xin, int in_mode, const flo
   a.in_rows = B * H * W * (stat_ranks > 1 ? stat_ranks : 1);       // SyncBatchNorm: the accumulator holds every rank's sums
   a.log2Cin = 0;
   while ((1 << a.log2Cin) < Cin) ++a.log2Cin;
-  const int pad = ksize >> 1;
-  a.Ho = (H + 2 * pad - ksize) / stride + 1; a.Wo = (W + 2 * pad - ksize) / stride + 1;
-  a.npix = B * a.Ho * a.Wo; a.ntiles = cdiv(a.npix, 16);
+  a.Ho = p.Ho; a.Wo = p.Wo; a.npix = p.npix; a.ntiles = p.ntiles;
   a.acc_out = acc_out;
   a.in_ps = (long)B * H * W * Cin; a.out_ps = (long)a.npix * Cout;
-  const int NT = Cout >= 64 ? 4 : Cout / 16;                       // 16 -> 1, 32 -> 2, >= 64 -> 4
-  const int gy = Cout / (NT * 16), nks = Kpad / 32;
+  a.TW = p.TW; a.TH = p.TH; a.IW = p.IW; a.IH = p.IH; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.ipw = p.ipw;
   hipStream_t s = (hipStream_t)stream;
-  // layers with >= 16 output pixels per row and whole 128 / 256-pixel blocks: the input block in LDS (wrn_conv_tile_kernel)
-  static const bool no_tile = SR_TUNE_ENV("SRHIP_CONV_NO_TILE") != nullptr;
-  if (!no_tile && ((a.Wo >= 16 && (a.Wo % 16) == 0) || (a.Wo == 8 && a.Ho == 8)) && NT >= 2 && Cin % 4 == 0) {
-    const int TW = (a.Wo % 32) == 0 ? 32 : (a.Wo == 8 ? 8 : 16);
-    // 128 pixels per workgroup (PG = 2); 256 (PG = 4: every filter fragment feeds four MFMAs) when the launch still has >= 4 workgroups per
-    // CU and the input block stays within 64 KB (two workgroups per CU)
-    auto geom = [&](int PG_) {
-      a.ipw = a.Wo == 8 ? PG_ : 1;
-      a.TW = TW; a.TH = 64 * PG_ / (TW * a.ipw); a.IW = (TW - 1) * stride + ksize; a.IH = (a.TH - 1) * stride + ksize;
-      a.tiles_x = a.Wo / TW; a.tiles_y = a.Ho / a.TH;
-      return (size_t)a.ipw * a.IH * a.IW * (Cin + 8) * sizeof(bf16_t);
-    };
-    int PG = 4;
-    size_t smem = geom(4);
-    if ((long)B * passes * a.Ho * a.Wo / 256 * gy < 1024 || a.Ho % a.TH != 0 || smem > 64 * 1024) { PG = 2; smem = geom(2); }
-    if (a.Wo == 8) {                                                 // the 8 x 8 stage: whole images, two per workgroup when the batch is even
-      PG = (B % 2 == 0) ? 2 : 1;
-      smem = geom(PG);
-      if (smem > 64 * 1024 && PG == 2) { PG = 1; smem = geom(1); }   // (the stride-2 layer into this stage: 17 x 17 input pixels per image)
-    }
-    if (a.Ho % a.TH == 0) {
-      if (smem <= 64 * 1024) {
-        const dim3 grid(B / a.ipw * a.tiles_x * a.tiles_y, gy, passes);
+  if (p.kernel >= 100) {
+    const size_t smem = p.smem;
+    const dim3 grid(p.grid_x, p.gy, passes);
 #define SR_TILE_LAUNCH(NT_, PG_)                                                                                           \
-        do {                                                                                                              \
-          auto kern = wrn_conv_tile_kernel<NT_, PG_>;                                                                     \
-          if (smem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-          SR_LAUNCH(kern, grid, dim3(256), smem, s, a);                                                                   \
-        } while (0)
-        if (PG == 1 && NT == 4) SR_TILE_LAUNCH(4, 1);
-        else if (PG == 1) SR_TILE_LAUNCH(2, 1);
-        else if (NT == 4 && PG == 4) SR_TILE_LAUNCH(4, 4);
-        else if (NT == 4) SR_TILE_LAUNCH(4, 2);
-        else if (PG == 4) SR_TILE_LAUNCH(2, 4);
-        else SR_TILE_LAUNCH(2, 2);
-#undef SR_TILE_LAUNCH
-        g_last_conv_plan = 100 + 10 * (NT == 4 ? 4 : 2) + PG;
-        SR_CHECK_LAUNCH();
-        return SR_OK;
-      }
+    do {                                                                                                                  \
+      auto kern = wrn_conv_tile_kernel<NT_, PG_>;                                                                         \
+      if (smem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
+      SR_LAUNCH(kern, grid, dim3(256), smem, s, a);                                                                       \
+    } while (0)
+    switch (p.kernel) {
+      case 141: SR_TILE_LAUNCH(4, 1); break;
+      case 121: SR_TILE_LAUNCH(2, 1); break;
+      case 144: SR_TILE_LAUNCH(4, 4); break;
+      case 142: SR_TILE_LAUNCH(4, 2); break;
+      case 124: SR_TILE_LAUNCH(2, 4); break;
+      case 122: SR_TILE_LAUNCH(2, 2); break;
+      default: return SR_EINVAL;
     }
+#undef SR_TILE_LAUNCH
+    g_last_conv_plan = p.kernel;
+    SR_CHECK_LAUNCH();
+    return SR_OK;
   }
-  // <= 512 workgroups (tools/wrn_conv_bench.py: 1024 cost +2.6 us with the statistics prologue / epilogue per workgroup); the waves of a
-  // workgroup split K (2 or 4 ways) until the launch has ~2048 waves, as long as a wave keeps >= 4 k steps
-  static const int env_ks = SR_TUNE_ENV("SRHIP_CONV_KSPLIT") ? atoi(SR_TUNE_ENV("SRHIP_CONV_KSPLIT")) : 0;          // tuning: force 1 / 2 / 4
-  static const int env_maxwg = SR_TUNE_ENV("SRHIP_CONV_MAXWG") ? atoi(SR_TUNE_ENV("SRHIP_CONV_MAXWG")) : 512;
-  int KS = 1;
-  while (KS < 4 && (long)a.ntiles * passes * gy * KS * 2 <= 2048 && nks / (KS * 2) >= 4) KS *= 2;
-  if (env_ks == 1 || env_ks == 2 || env_ks == 4) KS = env_ks;
-  // workgroups per pass: the launch as a whole stays at <= env_maxwg workgroups (two rounds of the chip) however many passes share it --
-  // every workgroup pays the statistics prologue / epilogue once and then walks more pixel tiles
-  int gx = cdiv(a.ntiles, 4 / KS);
-  const int cap = env_maxwg * (passes > 1 ? 2 : 1) / (gy * passes);
-  if (gx > cap) gx = cap;
-  if (gx < 1) gx = 1;
+  const int KS = p.KS;
+  const dim3 grid(p.grid_x, p.gy, passes);
 #define SR_CONV_LAUNCH(NT_)                                                                                          \
-  if (KS == 4) SR_LAUNCH((wrn_conv_kernel<NT_, 4>), dim3(gx, gy, passes), dim3(256), 0, s, a);                      \
-  else if (KS == 2) SR_LAUNCH((wrn_conv_kernel<NT_, 2>), dim3(gx, gy, passes), dim3(256), 0, s, a);                 \
-  else SR_LAUNCH((wrn_conv_kernel<NT_, 1>), dim3(gx, gy, passes), dim3(256), 0, s, a)
-  if (NT == 4) { SR_CONV_LAUNCH(4); }
-  else if (NT == 2) { SR_CONV_LAUNCH(2); }
-  else if (NT == 1) { SR_CONV_LAUNCH(1); }
+  if (KS == 4) SR_LAUNCH((wrn_conv_kernel<NT_, 4>), grid, dim3(256), 0, s, a);                                      \
+  else if (KS == 2) SR_LAUNCH((wrn_conv_kernel<NT_, 2>), grid, dim3(256), 0, s, a);                                 \
+  else SR_LAUNCH((wrn_conv_kernel<NT_, 1>), grid, dim3(256), 0, s, a)
+  if (p.NT == 4) { SR_CONV_LAUNCH(4); }
+  else if (p.NT == 2) { SR_CONV_LAUNCH(2); }
+  else if (p.NT == 1) { SR_CONV_LAUNCH(1); }
   else return SR_EINVAL;
 #undef SR_CONV_LAUNCH
-  g_last_conv_plan = 10 * NT + KS;
+  g_last_conv_plan = p.kernel;
   SR_CHECK_LAUNCH();
   return SR_OK;
 }

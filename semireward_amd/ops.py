@@ -1220,8 +1220,24 @@ def bn_acc_doubles(C):
 
 def wrn_conv_last_kernel():
     """Name of the kernel template the last srhip_wrn_conv_bn[_passes] call launched (srhip_wrn_conv_last_plan)."""
-    c = int(_lib.lib().srhip_wrn_conv_last_plan())
+    return wrn_conv_kernel_name(int(_lib.lib().srhip_wrn_conv_last_plan()))
+
+
+WrnConvPlan = collections.namedtuple("WrnConvPlan", "kernel grid_x rounds")
+
+
+def wrn_conv_kernel_name(c):
     return "wrn_conv_tile_kernel<%d, %d>" % ((c - 100) // 10, c % 10) if c >= 100 else "wrn_conv_kernel<%d, %d>" % (c // 10, c % 10)
+
+
+def wrn_conv_plan(B, H, W, Cin, Cout, ksize, stride, passes=1):
+    """What srhip_wrn_conv_bn[_passes] launches for this shape (host logic, no launch; srhip_wrn_conv_plan): the kernel template by the name
+    wrn_conv_last_kernel() gives, gridDim.x, and the direct kernel's grid-stride loop count (1 for the tile kernel)."""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    rc = int(_lib.lib().srhip_wrn_conv_plan(B, H, W, Cin, Cout, ksize, stride, int(passes), *[ctypes.addressof(x) for x in v]))
+    if rc != 0:
+        _lib.check(rc, "srhip_wrn_conv_plan")
+    return WrnConvPlan(wrn_conv_kernel_name(v[0].value), v[1].value, v[2].value)
 
 
 def wrn_conv_bn(xin, in_mode, in_stats, in_acc, in_gamma, in_beta, in_eps, slope, Wb, resid, y, B, H, W, Cin, Cout, ksize, stride, Kpad,

@@ -48,6 +48,18 @@ def test_invalid_arguments_return_error_codes_without_gpu():
         assert lib.srhip_attn_fwd(None, None, None, B, N, H, 0.125, None) == -1, (B, N, H)
         assert lib.srhip_attn_bwd(0x10000, 0x10000, 0x10000, 0x10000, 0x10000, 0x10000, B, N, H, 0.125, None) == -1, (B, N, H)
     assert lib.srhip_attn_plan(1365, 512, 12, None, None, None, None) == 0
+    # srhip_wrn_conv_plan refuses what srhip_wrn_conv_bn_passes refuses (B, H, W, Cin, Cout, k, stride, passes): a zero extent, a kernel size
+    # other than 1 / 3, Cin no power of two in [8, 128], Cout outside {16, 32, 64 n <= 256}, stride 0, passes outside [1, 64]
+    a = 0x10000                                                                                           # (never dereferenced)
+    for shape in [(0, 8, 8, 16, 32, 3, 1, 1), (2, 0, 8, 16, 32, 3, 1, 1), (2, 8, 0, 16, 32, 3, 1, 1), (2, 8, 8, 16, 32, 5, 1, 1), (2, 8, 8, 4, 32, 3, 1, 1),
+                  (2, 8, 8, 24, 32, 3, 1, 1), (2, 8, 8, 256, 32, 3, 1, 1), (2, 8, 8, 16, 48, 3, 1, 1), (2, 8, 8, 16, 320, 3, 1, 1),
+                  (2, 8, 8, 16, 32, 3, 0, 1), (2, 8, 8, 16, 32, 3, 1, 0), (2, 8, 8, 16, 32, 3, 1, 65)]:
+        B, H, W, Cin, Cout, k, s, P = shape
+        Kp = (Cin * k * k + 31) // 32 * 32
+        assert lib.srhip_wrn_conv_plan(*shape, None, None, None) == -1, shape
+        assert lib.srhip_wrn_conv_bn_passes(a, 2, None, None, None, None, None, 1e-3, 0.1, None, None, None, None, 0.0, 0, a, None, a, B, H, W, Cin,
+                                            Cout, k, s, Kp, None, 1, P, None) == -1, shape
+    assert lib.srhip_wrn_conv_plan(2, 8, 8, 16, 32, 3, 1, 64, None, None, None) == 0             # (any out pointer may be NULL)
     assert lib.srhip_layernorm_fwd(None, None, None, 1e-6, None, None, None, 4, 100, None) == -1
     assert lib.srhip_rewarder_fwd(None, None, None, None, None, None, 2, 8, 384, 100, 1, None) == -1     # save needs G == 1
     # audio front end (w2v_ops.hip): the guards reject before any launch.  The pointers are 16-byte aligned host addresses that are never
@@ -490,6 +502,35 @@ def test_attention_dispatch_is_pinned_per_shape_family():
     assert {k: tuple(ops.attn_plan(*k)) for k in want} == want
     with pytest.raises(RuntimeError):
         ops.attn_plan(1, 513, 1)
+
+
+def test_wrn_convolution_dispatch_is_pinned_per_shape_family():
+    """srhip_wrn_conv_plan (the host decisions of srhip_wrn_conv_bn_passes, no launch; the launcher reads the same function): the template,
+    gridDim.x and the direct kernel's loop count of the layers the WideResNet-28-2 step launches (64 images x 9 passes, and one pass), and both
+    sides of the thresholds between templates."""
+    from semireward_amd import ops
+    D, T = "wrn_conv_kernel<%d, %d>", "wrn_conv_tile_kernel<%d, %d>"
+    want = {    # (B, H, W, Cin, Cout, k, stride, passes): (kernel, grid_x, rounds)
+        (64, 32, 32, 16, 32, 3, 1, 9): (T % (2, 4), 256, 1),          # the 32 x 32 stage of the step: 256-pixel blocks
+        (64, 32, 32, 32, 32, 3, 1, 9): (T % (2, 4), 256, 1),
+        (64, 32, 32, 32, 64, 3, 2, 9): (T % (4, 2), 128, 1),          # stride 2 into 16 x 16: TW = 16, the PG = 4 block would need 33 input rows
+        (64, 16, 16, 64, 64, 3, 1, 9): (T % (4, 2), 128, 1),
+        (64, 16, 16, 64, 128, 3, 2, 9): (T % (4, 1), 64, 1),          # into 8 x 8: two images' 17 x 17 input blocks are 83 232 bytes, one is 41 616
+        (64, 8, 8, 128, 128, 3, 1, 9): (T % (4, 2), 32, 1),           # the 8 x 8 stage: two images per workgroup
+        (64, 32, 32, 16, 32, 3, 1, 1): (T % (2, 2), 512, 1),          # one pass: 256 blocks x gy = 1 < 1024
+        (64, 32, 32, 32, 16, 3, 1, 1): (D % (1, 1), 512, 2),          # Cout' = 16, the input gradient of the first stage (NT = 1 has no tile kernel): 4096 tiles, 2048 per round
+        (4, 32, 32, 16, 32, 3, 1, 64): (T % (2, 4), 16, 1),           # 1024 blocks x gy = 1: the first size with PG = 4 ...
+        (4, 32, 32, 16, 32, 3, 1, 63): (T % (2, 2), 32, 1),           # ... and the last without
+        (2, 24, 24, 16, 16, 3, 1, 64): (D % (1, 1), 16, 2),           # 72 tiles per pass over 16 workgroups x 4 waves
+        (2, 16, 16, 128, 128, 1, 2, 1): (T % (4, 1), 2, 1),           # 61 200 bytes of LDS: above the 48 KiB opt-in, below 64 KiB
+        (2, 16, 16, 128, 128, 3, 2, 1): (D % (4, 4), 8, 1),           # 78 608 bytes: back to the direct kernel
+        (2, 16, 8, 16, 32, 3, 1, 1): (D % (2, 1), 4, 1),              # Wo = 8 needs Ho = 8
+        (3, 8, 8, 16, 32, 3, 1, 1): (T % (2, 1), 3, 1),               # odd batch: one image per workgroup
+        (1, 3, 3, 128, 256, 3, 1, 1): (D % (4, 4), 1, 1),
+    }
+    assert {k: tuple(ops.wrn_conv_plan(*k)) for k in want} == want
+    with pytest.raises(RuntimeError):
+        ops.wrn_conv_plan(2, 8, 8, 24, 32, 3, 1)
 
 
 def test_weight_gradient_table_of_the_persistent_kernel_is_balanced_on_the_host():
