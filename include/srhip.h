@@ -608,6 +608,21 @@ int srhip_score_commit(const long long* label, const float* conf, const float* m
                        unsigned char* t_reward_keep, unsigned char* t_selected, int* t_count, void* stream);
 /* srhip_reward_mask2 over `total` rows in groups of B, the last group holding the rows that are left (its own mean over those rows). */
 int srhip_reward_mask2_ragged(const float* reward, float* mask2, float* mean_out, int total, int B, void* stream);
+/* The opt-in top-k reward filter (reward_filter: topk; the reference has the mean rule only).  `total` rows in `groups` groups of B, the last
+ * group holding the total - (groups - 1) * B rows that are left.  Per group, the rows are ordered: non-NaN before NaN, larger reward first
+ * with -0 == +0, lower index first among equal rewards; mask2[i] = 1.0 for the first min(kk, non-NaN rows of the group) rows of that order
+ * and 0.0 for the rest, with kk = k, and k_last for the last group.  A NaN reward is never kept; kk >= rows keeps every non-NaN row.
+ * Equivalently rank(i) = #{j : c(j) > c(i)} on c = (ordered_key(reward) << 32) | (0xFFFFFFFF - index), ordered_key the sign-flip map of the
+ * fp32 bits with NaN mapped to 0 and -0 canonicalised, and row i is kept iff rank(i) < kk and reward[i] is no NaN.
+ * peers (optional, fp32 [n_peers, groups * B], the tables of the data-parallel ranks, peers[self_peer] equal to reward): the candidates of a
+ * group are its rows on ALL peers, the index of a candidate is peer * B + row, kk counts over all of them, and the mask is written for the
+ * caller's own rows only.  peers NULL: n_peers 0 or 1, self_peer 0.
+ * One launch, no atomics, no sort, no host synchronisation, no allocation: capturable, equal inputs give equal bits; exactly the `total`
+ * words of mask2 are written.  O(B * B * n_peers) compares per group.
+ * SR_EINVAL before any launch: reward or mask2 NULL, groups / B / total < 1, k or k_last < 1, groups != ceil(total / B), groups * B >= 2^31,
+ * B * n_peers > 65536, self_peer outside [0, n_peers). */
+int srhip_reward_topk_mask(const float* reward, float* mask2, int groups, int B, int total, int k, int k_last, const float* peers,
+                           int n_peers, int self_peer, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Rewarder / Generator (K10, K14, K15).  params: flat fp32 block in named_parameters() order.

@@ -105,6 +105,7 @@ SIGNATURES = {
     "srhip_score_rows": (I, [P, c_longlong, I, I, I, F, P, P, P, P, I, P, P, P, P, P, P, P, P, P]),
     "srhip_score_commit": (I, [P, P, P, P, P, P, P, P, c_longlong, I, c_longlong, P, P, P, P, P, P, P, P, P, P]),
     "srhip_reward_mask2_ragged": (I, [P, P, P, I, I, P]),
+    "srhip_reward_topk_mask": (I, [P, P, I, I, I, I, I, P, I, I, P]),
     "srhip_rewarder_param_count": (L, [I, I]),
     "srhip_rewarder_ws_floats": (L, [I, I]),
     "srhip_generator_param_count": (L, [I]),

@@ -25,6 +25,7 @@ from ..nets import vit as _vit
 from ..core.algorithmbase import AlgorithmBase, DeferredScalar
 from ..core.registry import ALGORITHMS
 from .hooks import FixedThresholdingHook, FlexMatchThresholdingHook, PseudoLabelingHook
+from .reward_filter import read_reward_filter
 from .semireward import FlatAdam, Generator, Rewarder, cosine_target, label_dim
 from .utils import SSL_Argument, str2bool
 
@@ -448,6 +449,7 @@ class SRConsistencyBase(AlgorithmBase):
         self.grad_rows_precision = grad_rows_precision(args, backbone_class(net_builder))
         self.share_pass_prefixes = share_pass_prefixes(args, backbone_class(net_builder))
         _refuse_split_calls_on_batchnorm(args, backbone_class(net_builder))
+        self.reward_filter = read_reward_filter(args)        # mean (the reference's rule) unless the yaml opts into topk / fixed
         super().__init__(args, net_builder, tb_log, logger)
         read_rows_precision(argparse.Namespace(read_rows_precision=self.read_rows_precision), type(self.model))
         grad_rows_precision(argparse.Namespace(grad_rows_precision=self.grad_rows_precision), type(self.model))
@@ -847,8 +849,10 @@ class SRConsistencyBase(AlgorithmBase):
             # the weak rows of passes 1 .. K, scored where they are in the feature table (group g = rows (g + 1) * Bt + nl .. + nu)
             reward = self.rewarder.score_in_place(Fe, Bt + nl, Bt, nu, mi[nu:], groups=K)          # :99
             mask2 = torch.empty_like(reward)
-            mean_in = self.dp.reward_means(reward, K).contiguous() if (self.dp.global_reward_threshold and self.dp.active) else None
-            ops.reward_mask2(reward, mask2, None, K, nu, mean_in=mean_in)                          # :100-101
+            rf, glob = self.reward_filter, self.dp.global_reward_threshold and self.dp.active
+            mean_in = self.dp.reward_means(reward, K).contiguous() if (glob and rf.kind == "mean") else None
+            peers = self.dp.gather_rewards(reward) if (glob and rf.kind == "topk") else None
+            rf.apply(reward, mask2, K, nu, mean_in=mean_in, peers=peers, self_peer=self.dp.rank)    # :100-101 (mean: ops.reward_mask2)
         self._join_grad()                                  # from here on the labelled / strong rows of the loss are read
         # the upstream gradient of the gradient rows (labelled rows of pass 0 | strong rows of the last pass) is ONE buffer the two loss
         # launches fill (the fairness rows of FreeMatch with K > 0 sit between them: that case still concatenates)

@@ -106,7 +106,9 @@ class SRPseudoLabel(SRConsistencyBase):
             self.rewarder.eval()
             reward = self.rewarder.score(Fw[nu:].contiguous(), mi[nu:], groups=K)                   # :84
             mask2 = torch.empty_like(reward)
-            ops.reward_mask2(reward, mask2, None, K, nu)                                            # :85-86
+            rf = self.reward_filter
+            peers = self.dp.gather_rewards(reward) if (rf.kind == "topk" and self.dp.global_reward_threshold and self.dp.active) else None
+            rf.apply(reward, mask2, K, nu, peers=peers, self_peer=self.dp.rank)                      # :85-86 (mean: ops.reward_mask2)
             unsup_loss, dl_u = self.consistency_loss(Lw[K * nu:], mi[K * nu:], "ce", mask=masks[K], mask2=mask2[(K - 1) * nu:],
                                                      grad_scale=self.lambda_u * warm)               # :87
         else:

@@ -3,7 +3,7 @@ pseudo-label now and with which label, how confident it is, and which of them th
 
 Per batch, after the backbone's inference forward, four kinds of launches and nothing else: ``ops.score_rows`` (label, confidence, margin,
 entropy and the algorithm's mask / weight from its threshold state as it stands), the Rewarder's forward in groups of ``reward_group`` rows,
-``ops.reward_mask2`` and ``ops.score_commit`` (the scatter into the table).  No torch indexing op, no allocation after the first batch, no
+``ops.reward_mask2`` (or the launch of the algorithm's opt-in ``reward_filter``) and ``ops.score_commit`` (the scatter into the table).  No torch indexing op, no allocation after the first batch, no
 host synchronisation, and no training state is written: the thresholds, the Rewarder, the DropPath counter and ``it`` are where they were.
 
 ``PseudoLabelTable`` owns the columns, one entry per unlabelled sample:
@@ -203,6 +203,8 @@ def score_loader(alg, net, loader, n, reward_group):
     F, L = rw.feature_dim, rw.label_dim
     meta = dict(algorithm=alg.algorithm, it=int(alg.it), mode=mode, p_cutoff=kw.get("p_cutoff"), reward_group=int(reward_group),
                 state={k: v.detach().cpu().numpy().copy() for k, v in state.items()})
+    rf = alg.reward_filter
+    meta.update(rf.meta(int(reward_group)))
     table = PseudoLabelTable(n, alg.device, alg.num_classes, meta)
     scratch, seen, g = None, 0, int(reward_group)
     with ops.stream_scope():
@@ -223,7 +225,7 @@ def score_loader(alg, net, loader, n, reward_group):
             if r:
                 ops.rewarder_fwd(rw.flat, rw.flat_t, ops.RawRows(feat, G * g * F), ops.RawRows(scratch.cols["label"], G * g),
                                  ops.RawRows(scratch.reward, G * g), rw._workspace(1, r), 1, r, F, L)
-            ops.reward_mask2(scratch.reward, scratch.keep, None, G + (1 if r else 0), g, total=B)
+            rf.apply(scratch.reward, scratch.keep, G + (1 if r else 0), g, total=B)       # the algorithm's reward filter (mean: ops.reward_mask2)
             ops.score_commit(scratch.cols, scratch.reward, scratch.keep, table.columns, B, idx=idx, row_offset=seen)
             seen += B
     return table

@@ -245,6 +245,69 @@ __global__ __launch_bounds__(64) void reward_mask2_kernel(const float* __restric
   if (mean_out && lane == 0) mean_out[blockIdx.x] = mean;
 }
 
+// Top-k reward filter (opt-in, reward_filter: topk): mask2[g, i] = 1 for the k best rows of group g, 0 for the rest.
+// Order: non-NaN before NaN, larger reward first (-0 == +0), lower candidate index first among equal rewards; a NaN row is never kept.
+// Rank by counting, no sort and no atomics: rank(i) = #{j : key(j) > key(i) or (key(j) == key(i) and j < i)} over the group's candidates,
+// key = the sign-flip map of the fp32 bits (unsigned order == float order; denormals keep their order whatever the float mode) with -0
+// canonicalised and NaN mapped to 0, below every number (-Inf maps to 0x007fffff).  Row i is kept iff rank(i) < k and it is no NaN.
+// Grid (groups, row slices of blockDim.x): a thread owns one row; the candidate keys pass through LDS in tiles of TOPK_TILE (16-byte global
+// loads, head and tail peeled to the alignment of the group's first row) and are read back four per ds_read as broadcasts while every
+// thread counts.  The tile is padded to a multiple of four with key 0, which no numbered row counts.
+// peers != NULL: the candidates of group g are its rows on all n_peers tables (candidate index peer * Bg + row); the rows ranked and
+// written are the caller's own (reward, its index self_peer * Bg + row).
+constexpr int TOPK_TILE = 2048;
+
+__device__ __forceinline__ uint32_t topk_key(float r) {
+  uint32_t u = __float_as_uint(r);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;            // NaN: last
+  if (u == 0x80000000u) u = 0u;                               // -0 == +0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__global__ __launch_bounds__(256) void reward_topk_kernel(const float* __restrict__ reward, float* __restrict__ mask2,
+                                                         const float* __restrict__ peers, int n_peers, int self_peer, int groups, int Bg,
+                                                         int total, int k, int k_last) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_key[TOPK_TILE];
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int g = blockIdx.x; g < groups; g += gridDim.x) {
+    const size_t g0 = (size_t)g * Bg;
+    const int B = min(Bg, total - g * Bg);                    // rows of this group (the last one may be ragged)
+    if ((int)(blockIdx.y * nt) >= B) continue;                // (the whole workgroup: no barrier is skipped by a part of it)
+    const int i = blockIdx.y * nt + tid;
+    const bool own = i < B;
+    const uint32_t ki = own ? topk_key(reward[g0 + i]) : 0u;
+    const int kk = g == groups - 1 ? k_last : k;
+    int rank = 0;
+    for (int p = 0; p < n_peers; ++p) {
+      const float* src = peers ? peers + (size_t)p * groups * Bg + g0 : reward + g0;
+      for (int t = 0; t < B; t += TOPK_TILE) {
+        const int n = min(TOPK_TILE, B - t);
+        const float* s = src + t;
+        const int head = min(n, (int)((4u - (uint32_t)(((uintptr_t)s >> 2) & 3u)) & 3u));
+        const int nv = (n - head) >> 2;
+        for (int j = tid; j < head; j += nt) s_key[j] = topk_key(s[j]);
+        for (int v = tid; v < nv; v += nt) {
+          const f32x4_t x = *reinterpret_cast<const f32x4_t*>(s + head + 4 * v);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) s_key[head + 4 * v + e] = topk_key(x[e]);
+        }
+        for (int j = head + 4 * nv + tid; j < ((n + 3) & ~3); j += nt) s_key[j] = j < n ? topk_key(s[j]) : 0u;
+        __syncthreads();
+        // candidate jj of this tile has index p * Bg + t + jj: among equal keys it goes first iff jj < lim.  key(j) >= key(i) is
+        // key(j) > key(i) - 1 (a numbered row's key is >= 0x007fffff; a NaN row's rank is never read)
+        const int lim = (self_peer - p) * Bg + i - t;
+        for (int jj = 0; jj < n; jj += 4) {
+          const u32x4_t c = *reinterpret_cast<const u32x4_t*>(s_key + jj);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) rank += c[e] > ki - (jj + e < lim ? 1u : 0u) ? 1 : 0;
+        }
+        __syncthreads();
+      }
+    }
+    if (own) mask2[g0 + i] = (ki != 0u && rank < kk) ? 1.0f : 0.0f;
+  }
+}
+
 // Masked cross-entropy forward + analytic backward.  ONE workgroup (B is the per-GPU batch).
 //   loss = coef_out * mean_i( nll_i * mask_i * mask2_i )         (consistency.py:38-45: mean over ALL rows)
 //   dlogits[i, c] = grad_scale * (softmax_ic - [c == y_i]) * mask_i * mask2_i / B
@@ -561,6 +624,20 @@ extern "C" int srhip_reward_mask2_ragged(const float* reward, float* mask2, floa
   if (!reward || !mask2 || total <= 0 || B <= 0) return SR_EINVAL;
   SR_LAUNCH(reward_mask2_kernel, dim3(cdiv(total, B)), dim3(64), 0, (hipStream_t)stream, reward, mask2, mean_out, (const float*)nullptr, B,
             total);
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+
+extern "C" int srhip_reward_topk_mask(const float* reward, float* mask2, int groups, int B, int total, int k, int k_last,
+                                      const float* peers, int n_peers, int self_peer, void* stream) {
+  if (!reward || !mask2 || groups <= 0 || B <= 0 || total <= 0 || k < 1 || k_last < 1) return SR_EINVAL;
+  if ((long long)groups * B > 0x7fffffffll || total > (long long)groups * B || total <= (long long)(groups - 1) * B) return SR_EINVAL;
+  if (peers ? (n_peers < 1 || self_peer < 0 || self_peer >= n_peers) : (n_peers > 1 || self_peer != 0)) return SR_EINVAL;
+  const int np = peers ? n_peers : 1;
+  if ((long long)B * np > 65536) return SR_EINVAL;
+  const int nt = B <= 64 ? 64 : 256;                          // a group of up to one wave of rows: one wave
+  SR_LAUNCH(reward_topk_kernel, dim3(groups < (1 << 20) ? groups : (1 << 20), cdiv(B, nt)), dim3(nt), 0, (hipStream_t)stream, reward, mask2, peers, np,
+            peers ? self_peer : 0, groups, B, total, k, k_last);
   SR_CHECK_LAUNCH();
   return SR_OK;
 }

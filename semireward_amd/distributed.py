@@ -354,6 +354,16 @@ class DataParallel:
             return packed[:-1] / packed[-1]
         return s / B
 
+    def gather_rewards(self, reward):
+        """Every rank's rewards of the step, [world, K * nu] in rank order (row ``rank`` = ``reward``): the peer table of the global top-k
+        reward filter (reward_filter: topk with global_reward_threshold) -- ONE all-gather of K * nu floats per step."""
+        r = reward.contiguous().view(-1)
+        if not self.active:
+            return r.view(1, -1)
+        out = torch.empty(self.world_size, r.numel(), dtype=r.dtype, device=r.device)
+        dist.all_gather_into_tensor(out.view(-1), r)          # (the concatenated form: gloo takes no [world, n] output)
+        return out
+
 
 def shard_indices(n, rank, world):
     """DistributedSampler rank-stride sharding of the reference (semilearn/datasets/samplers/sampler.py:70): perm[rank::world]."""

@@ -896,6 +896,18 @@ def reward_mask2(reward, mask2, mean_out, groups, B, mean_in=None, total=None):
     _call("srhip_reward_mask2", _p(reward), _p(mask2), _p(mean_out), _p(mean_in), groups, B, _s())
 
 
+def reward_topk_mask(reward, mask2, groups, B, k, total=None, k_last=None, peers=None, self_peer=0):
+    """The opt-in top-k reward filter (srhip_reward_topk_mask): per group of B rows the k best rewards, NaN never, ties to the lower index.
+    total (rows in all, groups == ceil(total / B)): the last group holds the rows that are left and keeps k_last (default k) of them.
+    peers fp32 [n_peers, groups * B] (row ``self_peer`` equal to ``reward``): the candidates of a group are its rows on every peer."""
+    total = groups * B if total is None else total
+    n_peers = 0 if peers is None else int(peers.shape[0])
+    if _CHECK_ARGS and peers is not None:
+        assert peers.dim() == 2 and peers.shape[1] == groups * B and peers.dtype == torch.float32
+    _call("srhip_reward_topk_mask", _p(reward), _p(mask2), groups, B, total, int(k), int(k if k_last is None else k_last), _p(peers), n_peers,
+          int(self_peer) if peers is not None else 0, _s())
+
+
 def masked_ce(logits, targets, mask, mask2, grad_scale, loss_out, dlogits, B, C):
     _call("srhip_masked_ce", _p(logits), _p(targets), _p(mask), _p(mask2), grad_scale, _p(loss_out), _p(dlogits), B, C, _s())
 
