@@ -111,21 +111,18 @@ class AlgorithmBase:
         if monitor:                                          # refused from the yaml keys, before a dataset is looked at
             from .pl_monitor import PlMonitor
             PlMonitor.check_targets(g("ulb_targets"))
+        self.input_mode = None                               # the record of the one device input mode that is on (data/modes.py)
+        if self.device_data or self.device_audio or self.device_tokens:      # no key: nothing under data/ is imported
+            from ..data.modes import active_mode
+            self.input_mode = active_mode(args)
         self.dataset_dict = self.set_dataset()
         if monitor:                                          # off: no attribute, no allocation, no launch, the same log keys
             self.pl_monitor = PlMonitor(args.ulb_targets, self.num_classes, self.device, g("ulb_dest_len") or None)
             self._monitor_idx_ulb = None
         self.loader_dict = self.set_data_loader()
         self.model = self.set_model()
-        if self.device_data:
-            from ..data.device_loader import refuse_unsupported_model
-            refuse_unsupported_model(self.model)
-        if self.device_audio:
-            from ..data.device_audio import refuse_unsupported_model as refuse_unsupported_audio_model
-            refuse_unsupported_audio_model(self.model)
-        if self.device_tokens:               # a ValueError before any launch: max_length beyond max_pos, a stored id beyond the vocabulary
-            from ..data.device_tokens import refuse_unsupported_model as refuse_unsupported_token_model
-            refuse_unsupported_token_model(self.model, self.dataset_dict)
+        if self.input_mode is not None:      # refusals decided from the model: another kind of backbone; tokens: max_length beyond max_pos, a stored id beyond the vocabulary
+            self.input_mode.refuse_unsupported_model(self.model, self.dataset_dict)
         if self.model.couples_batch_rows:
             self.model.dp = self.dp          # BatchNorm backbone under data parallel = SyncBatchNorm, as the reference's send_model_cuda (misc.py:55)
         self.ema_model = self.set_ema_model()
@@ -136,7 +133,7 @@ class AlgorithmBase:
         self._hooks = []
         self.hooks_dict = OrderedDict()
         self.set_hooks()
-        if self.device_data or self.device_audio or self.device_tokens:      # the reference's DistSamplerSeedHook (algorithmbase.py:565); every other configuration keeps its hook list
+        if self.input_mode is not None:      # the reference's DistSamplerSeedHook (algorithmbase.py:565); every other configuration keeps its hook list
             self.register_hook(DistSamplerSeedHook(), None, "NORMAL")
 
     def init(self, **kwargs):
@@ -148,27 +145,14 @@ class AlgorithmBase:
         when ``semilearn`` is importable (or by the functions handed in as ``args.data_functions = (get_dataset, get_data_loader)``), with the
         reference's rank-0-first barriers and its ``ulb_dest_len`` / ``lb_dest_len`` side effects on ``args``.  ``args.dataset_dict``: a ready
         dict is taken as is.  Otherwise None -- ``train(batches=...)`` or a ``loader_dict`` assigned by the caller feeds the loop."""
-        a = self.args
-        if self.device_tokens:                # refused from the yaml keys, before a dataset is looked at (first: it names a sibling key set beside it)
-            from ..data.device_tokens import refuse_unsupported as refuse_unsupported_tokens
-            refuse_unsupported_tokens(a)
-        if self.device_audio:                 # refused from the yaml keys, before a dataset is looked at
-            from ..data.device_audio import refuse_unsupported as refuse_unsupported_audio
-            refuse_unsupported_audio(a)
+        a, mode = self.args, self.input_mode
+        if mode is not None and mode.refuse_early:       # refused from the yaml keys, before a dataset is looked at
+            mode.refuse_unsupported(a)
         ready = getattr(a, "dataset_dict", None)
         get_dataset = (getattr(a, "data_functions", None) or reference_data_functions())[0]
         if ready is None and (get_dataset is None or getattr(a, "dataset", None) is None):
-            if self.device_data:
-                raise RuntimeError("device_data: True needs the dataset arrays: pass args.dataset_dict (reference dataset objects, or plain "
-                                   "{'data': uint8 [n, H, W, 3], 'targets': ...} dicts), or install semilearn so that its get_dataset runs")
-            if self.device_audio:
-                raise RuntimeError("device_audio: True needs the clips: pass args.dataset_dict (reference dataset objects, or plain "
-                                   "{'data': [1-D float arrays], 'targets': ..., 'data_s': [[...], ...]} dicts), or install semilearn so that its "
-                                   "get_dataset runs")
-            if self.device_tokens:
-                raise RuntimeError("device_tokens: True needs the sentences: pass args.dataset_dict (reference dataset objects, or plain "
-                                   "{'data': [strings or 1-D token arrays], 'targets': ..., 'data_s': [[...], [...]]} dicts), or install semilearn "
-                                   "so that its get_dataset runs")
+            if mode is not None:
+                raise RuntimeError(mode.needs_datasets)
             return None
         if ready is None:
             if self.rank != 0 and self.distributed:
@@ -177,15 +161,8 @@ class AlgorithmBase:
                                 getattr(a, "include_lb_to_ulb", True))
         if ready is None:
             return None
-        if self.device_data:                  # uint8 arrays -> HBM, resized once to img_size (the transforms' leading Resize)
-            from ..data.device_loader import build_device_datasets
-            ready = build_device_datasets(a, ready, self.device)
-        if self.device_audio:                 # float clips -> one flat fp32 store in HBM
-            from ..data.device_audio import build_wave_datasets
-            ready = build_wave_datasets(a, ready, self.device)
-        if self.device_tokens:                # sentences and variants, tokenised once -> one flat int32 store in HBM
-            from ..data.device_tokens import build_token_datasets
-            ready = build_token_datasets(a, ready, self.device)
+        if mode is not None:                  # the arrays -> HBM: images resized once to img_size, clips / token rows in one flat store
+            ready = mode.build_datasets(a, ready, self.device)
         a.ulb_dest_len = len(ready["train_ulb"]) if ready.get("train_ulb") is not None else 0
         a.lb_dest_len = len(ready["train_lb"])
         self.print_fn("unlabeled data number: {}, labeled data number {}".format(a.ulb_dest_len, a.lb_dest_len))
@@ -199,25 +176,10 @@ class AlgorithmBase:
         a = self.args
         if self.dataset_dict is None:
             return getattr(a, "loader_dict", None)
-        if self.device_data:
-            from ..data.device_loader import build_device_loaders
-            self.print_fn("Create device-resident train and test data loaders")
-            ld = build_device_loaders(a, self.dataset_dict, list(signature(self.train_step).parameters), self.num_train_iter, self.epochs,
-                                      self.world_size if self.distributed else 1, self.rank if self.distributed else 0)
-            self.print_fn(f"[!] data loader keys: {ld.keys()}")
-            return ld
-        if self.device_audio:
-            from ..data.device_audio import build_wave_loaders
-            self.print_fn("Create device-resident waveform train and test data loaders")
-            ld = build_wave_loaders(a, self.dataset_dict, list(signature(self.train_step).parameters), self.num_train_iter, self.epochs,
-                                    self.world_size if self.distributed else 1, self.rank if self.distributed else 0, self.print_fn)
-            self.print_fn(f"[!] data loader keys: {ld.keys()}")
-            return ld
-        if self.device_tokens:
-            from ..data.device_tokens import build_token_loaders
-            self.print_fn("Create device-resident token train and test data loaders")
-            ld = build_token_loaders(a, self.dataset_dict, list(signature(self.train_step).parameters), self.num_train_iter, self.epochs,
-                                     self.world_size if self.distributed else 1, self.rank if self.distributed else 0)
+        if self.input_mode is not None:
+            self.print_fn(self.input_mode.loaders_line)
+            ld = self.input_mode.build_loaders(a, self.dataset_dict, list(signature(self.train_step).parameters), self.num_train_iter, self.epochs,
+                                               self.world_size if self.distributed else 1, self.rank if self.distributed else 0, self.print_fn)
             self.print_fn(f"[!] data loader keys: {ld.keys()}")
             return ld
         get_data_loader = (getattr(a, "data_functions", None) or reference_data_functions())[1]
@@ -505,7 +467,7 @@ class AlgorithmBase:
             raise NotImplementedError("score_unlabeled needs a SemiReward algorithm (a MaskingHook and a rewarder)")
         a = self.args
         if loader is None:
-            if not (self.device_data or self.device_audio or self.device_tokens):
+            if self.input_mode is None:
                 raise ValueError("score_unlabeled: pass loader= (an iterable of {'x_lb'} or {'x_ulb_w', 'idx_ulb'} batches); loader=None builds "
                                  "one only with device_data, device_audio or device_tokens")
             loader = unlabelled_eval_loader(self, int(batch_size or a.eval_batch_size))

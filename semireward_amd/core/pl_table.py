@@ -152,17 +152,7 @@ def unlabelled_eval_loader(alg, batch_size):
     view = copy.copy(ds)                 # the evaluation loaders want labels beside the rows; the unlabelled store has none: -1 (unknown), unused here
     if view.targets is None:
         view.targets = torch.full((len(ds),), -1, dtype=torch.int64, device=ds.device)
-    a = alg.args
-    if alg.device_data:
-        from ..data.augment import GpuAugment
-        from ..data.device_loader import DeviceEvalLoader, dataset_stats
-        mean, std = dataset_stats(a)
-        return DeviceEvalLoader(view, batch_size, GpuAugment(int(a.img_size), 0, mean, std, device=ds.device))
-    if alg.device_audio:
-        from ..data.device_audio import WaveEvalLoader, resolve_normalize, view_length
-        return WaveEvalLoader(view, batch_size, view_length(a), resolve_normalize(a, alg.print_fn))
-    from ..data.device_tokens import TokenEvalLoader
-    return TokenEvalLoader(view, batch_size)
+    return alg.input_mode.eval_loader(alg.args, view, batch_size, alg.print_fn)
 
 
 def _batch_rows(alg, data):

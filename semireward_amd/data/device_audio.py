@@ -22,17 +22,14 @@ import numpy as np
 import torch
 
 from .. import ops
-from .device_loader import ROLES, EpochSampler
+from .device_loader import ROLES, EpochSampler             # noqa: F401  (re-exported: tests and tools reach them through this module)
+from .modes import active_mode, build_loaders
+from .ragged import RaggedEvalLoader, RaggedStore, RaggedTrainLoader, _h2d, with_variants
 
 HUB_NAMES = {"wave2vecv2_base": "facebook/wav2vec2-base-960h", "hubert_base": "facebook/hubert-base-ls960"}     # the reference's collators (audio_collactor.py:115-124)
 DATA_S_HELP = ("the strong view must be precomputed: give the unlabelled set V >= 1 pre-augmented variants of every clip as "
                "{'data': [...], 'data_s': [[variant 0 of every clip], [variant 1 ...], ...]} (e.g. the reference's WaveformTransforms applied V times "
                "on a machine that has torchaudio; configs/README.md has the recipe)")
-
-
-def _h2d(t, device):
-    """Every host-to-device copy of the loaders goes through here (one per epoch and train loader; the tests count them)."""
-    return t.to(device)
 
 
 def _clips(data, what):
@@ -51,44 +48,15 @@ def _clips(data, what):
     return out
 
 
-class DeviceWaveDataset:
+class DeviceWaveDataset(RaggedStore):
     """Clips of any length in one flat fp32 device array ``store``; clip r occupies store[row_off[r] : row_off[r] + row_len[r]] and starts at
     a multiple of 4 floats (the gap is zero).  Rows 0 .. n - 1 are the clips; with ``data_s`` (V lists of n pre-augmented variants) row
     n (1 + v) + i is variant v of clip i (``strong_row``).  int64 targets resident too (None: unlabelled); ``targets_host`` / ``row_len_host`` /
     ``row_off_host`` keep numpy copies for the host side of a loader."""
 
     def __init__(self, data, targets, device, data_s=None):
-        clips = _clips(data, "data")
-        self.n = len(clips)
-        if self.n == 0:
-            raise ValueError("device_audio: the dataset holds no clip")
-        self.n_variants = 0
-        if data_s is not None:
-            for v, var in enumerate(data_s):
-                var = _clips(var, "data_s[%d]" % v)
-                if len(var) != self.n:
-                    raise ValueError("device_audio: data_s[%d] must hold one variant of every clip (%d), got %d" % (v, self.n, len(var)))
-                clips += var
-            self.n_variants = len(data_s)
-            if self.n_variants == 0:
-                raise ValueError("device_audio: data_s is empty; " + DATA_S_HELP)
-        self.device = torch.device(device)
-        self.row_len_host = np.array([c.size for c in clips], dtype=np.int32)
-        padded = (self.row_len_host.astype(np.int64) + 3) & ~np.int64(3)
-        self.row_off_host = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
-        flat = np.zeros(int(padded.sum()), dtype=np.float32)
-        for c, o in zip(clips, self.row_off_host):
-            flat[o:o + c.size] = c
-        self.store = torch.from_numpy(flat).to(self.device)
-        self.row_off = torch.from_numpy(self.row_off_host).to(self.device)
-        self.row_len = torch.from_numpy(self.row_len_host).to(self.device)
-        if targets is None:
-            self.targets = self.targets_host = None
-        else:
-            self.targets_host = np.asarray(targets.cpu() if torch.is_tensor(targets) else targets).astype(np.int64)
-            if self.targets_host.shape != (self.n,):
-                raise ValueError("targets must hold one label per clip (%d clips, targets of shape %s)" % (self.n, self.targets_host.shape))
-            self.targets = torch.from_numpy(self.targets_host).to(self.device)
+        clips, n, n_variants = with_variants(_clips, data, data_s, "device_audio", "clip", DATA_S_HELP)
+        super().__init__(clips, n, n_variants, targets, device, 0, "clip")
 
     @classmethod
     def from_reference(cls, dset, device):
@@ -96,16 +64,8 @@ class DeviceWaveDataset:
         {'data': [...], 'targets': ..., 'data_s': [[...], ...]} dict."""
         if isinstance(dset, cls):
             return dset
-        if isinstance(dset, dict):
-            return cls(dset["data"], dset.get("targets"), device, dset.get("data_s"))
-        ulb = bool(getattr(dset, "is_ulb", False))
-        return cls(dset.data, None if ulb else getattr(dset, "targets", None), device, getattr(dset, "data_s", None))
-
-    def strong_row(self, variant, index):
-        return self.n * (1 + np.asarray(variant, dtype=np.int64)) + np.asarray(index, dtype=np.int64)
-
-    def __len__(self):
-        return self.n
+        data, targets, data_s = cls.reference_fields(dset)
+        return cls(data, targets, device, data_s)
 
 
 def crop_offsets(rng, lens, L):
@@ -115,104 +75,51 @@ def crop_offsets(rng, lens, L):
     return np.where(lens <= L, 0, off).astype(np.int32)
 
 
-class WaveTrainLoader:
+class WaveTrainLoader(RaggedTrainLoader):
     """Per-step dicts of one epoch: consecutive ``batch_size`` chunks of the sampler's stream (drop_last).  'idx_*' the dataset indices, 'y_*'
     the targets, 'x_*' a crop of the clip and 'x_*_s' a crop of one of its pre-augmented variants, picked uniformly -- every view fp32
     [batch_size, L], one srhip_wave_view launch.  ``strong=False`` leaves the strong views out: not drawn, not launched.  The draws are a
     function of (``seed``, epoch): ``set_epoch`` / iterating again replays them.  Everything an epoch needs -- its index stream, targets, store
     rows and crop offsets -- goes to the device in ONE copy when the epoch starts; ``draws`` keeps the host arrays of the last epoch started:
     {view key: (store rows int64 [N], crop offsets int32 [N])}."""
+    mode_key, data_s_help = "device_audio", DATA_S_HELP
 
     def __init__(self, dataset, batch_size, sampler, L, normalize=True, strong=True, keys=("idx_lb", "x_lb", "y_lb"), seed=(0,)):
-        self.dataset, self.batch_size, self.sampler, self.L, self.normalize = dataset, int(batch_size), sampler, int(L), bool(normalize)
-        self.keys = tuple(k for k in keys if strong or not self._is_strong(k))
-        if any(k.startswith("y") for k in self.keys) and dataset.targets is None:
-            raise ValueError("a loader with a target key needs a labelled dataset")
-        if any(self._is_strong(k) for k in self.keys) and dataset.n_variants == 0:
-            raise ValueError("device_audio: a strong view was asked of a dataset without data_s; " + DATA_S_HELP)
-        self.seed = tuple(int(s) for s in seed)
-        self.epoch = 0
-        self.draws = {}
+        self.L, self.normalize = int(L), bool(normalize)
+        super().__init__(dataset, batch_size, sampler, strong, keys, seed)
 
-    @staticmethod
-    def _is_strong(k):
-        return k.startswith("x") and k.endswith("_s")
+    def _copy(self, table):
+        return _h2d(table, self.dataset.device)
 
-    def set_epoch(self, epoch):
-        self.epoch = int(epoch)
-        self.sampler.set_epoch(epoch)
+    def _draw(self, rng, key, src):
+        """One more table row behind the store rows: its first N int32 are the crop offsets."""
+        lens = self.dataset.row_len_host
+        crop = crop_offsets(rng, lens[src], self.L)
+        ops.check_wave_rows(src, crop, lens)
+        packed = np.zeros(src.size, dtype=np.int64)
+        packed.view(np.int32)[:src.size] = crop
+        return [packed], (src, crop)
 
-    def __len__(self):
-        return len(self.sampler) // self.batch_size
-
-    def _epoch_table(self):
-        """The epoch as one int64 host table [rows, N] and the meaning of its rows: {key: row} for 'idx' / 'y' keys, {key: (row of the store rows,
-        row whose first N int32 are the crop offsets)} for views."""
-        ds = self.dataset
-        self.sampler.set_epoch(self.epoch)
-        rng = np.random.Generator(np.random.PCG64(self.seed + (self.epoch,)))
-        stream = np.ascontiguousarray(self.sampler.indices(), dtype=np.int64)
-        N, rows, where, self.draws = stream.size, [], {}, {}
-        for k in self.keys:
-            if k.startswith("idx"):
-                where[k] = len(rows)
-                rows.append(stream)
-            elif k.startswith("y"):
-                where[k] = len(rows)
-                rows.append(ds.targets_host[stream])
-            else:
-                src = ds.strong_row(rng.integers(0, ds.n_variants, size=N), stream) if self._is_strong(k) else stream
-                crop = crop_offsets(rng, ds.row_len_host[src], self.L)
-                ops.check_wave_rows(src, crop, ds.row_len_host)
-                packed = np.zeros(N, dtype=np.int64)
-                packed.view(np.int32)[:N] = crop
-                where[k] = (len(rows), len(rows) + 1)
-                rows += [src, packed]
-                self.draws[k] = (src, crop)
-        return np.stack(rows), where, N
-
-    def __iter__(self):
-        ds, B = self.dataset, self.batch_size
-        table, where, N = self._epoch_table()
-        dev = _h2d(torch.from_numpy(table), ds.device)                                     # the epoch's one copy, sliced per step
-        i32 = dev.view(torch.int32)                                                        # [rows, 2 N]: the crop offsets of a view are [row, :N]
-        for s in range(0, len(self) * B, B):
-            out = {}
-            for k in self.keys:
-                w = where[k]
-                if isinstance(w, tuple):
-                    out[k] = ops.wave_view(ds.store, ds.row_off, ds.row_len, dev[w[0], s:s + B], i32[w[1], s:s + B], self.L, self.normalize)
-                else:
-                    out[k] = dev[w, s:s + B]
-            yield out
+    def _view_fn(self, dev, row, draw):
+        ds, B, L, normalize, wave_view = self.dataset, self.batch_size, self.L, self.normalize, ops.wave_view
+        store, row_off, row_len = ds.store, ds.row_off, ds.row_len
+        src, crop = dev[row], dev.view(torch.int32)[row + 1]                               # (as int32 the table is [rows, 2 N]: the crop offsets are the first N)
+        return lambda s, t: wave_view(store, row_off, row_len, src[s:s + B], crop[s:s + B], L, normalize)
 
 
-class WaveEvalLoader:
+class WaveEvalLoader(RaggedEvalLoader):
     """The dataset in order, last partial batch kept: {'x_lb', 'y_lb'} with every clip taken from its first sample, truncated to L and the
     batch padded to its own longest row (at most L) -- the reference's evaluation collator (``padding=True, truncation=True``).  The host
     knows the lengths: no synchronisation and no host-to-device copy."""
 
     def __init__(self, dataset, batch_size, L, normalize=True):
-        if dataset.targets is None:
-            raise ValueError("the evaluation loader needs a labelled dataset")
-        self.dataset, self.batch_size, self.L, self.normalize = dataset, int(batch_size), int(L), bool(normalize)
-        n = len(dataset)
-        self._rows = torch.arange(n, dtype=torch.int64, device=dataset.device)          # made on the device: nothing to copy
-        self._crop = torch.zeros(n, dtype=torch.int32, device=dataset.device)
+        super().__init__(dataset, batch_size)
+        self.L, self.normalize = int(L), bool(normalize)
+        self._crop = torch.zeros(len(dataset), dtype=torch.int32, device=dataset.device)
 
-    def __len__(self):
-        return -(-len(self.dataset) // self.batch_size)
-
-    def batch_lengths(self):
-        ds, n = self.dataset, len(self.dataset)
-        return [int(min(ds.row_len_host[s:min(s + self.batch_size, n)].max(), self.L)) for s in range(0, n, self.batch_size)]
-
-    def __iter__(self):
-        ds, n = self.dataset, len(self.dataset)
-        for s, S in zip(range(0, n, self.batch_size), self.batch_lengths()):
-            e = min(s + self.batch_size, n)
-            yield {"x_lb": ops.wave_view(ds.store, ds.row_off, ds.row_len, self._rows[s:e], self._crop[s:e], S, self.normalize),
-                   "y_lb": ds.targets[s:e]}
+    def _view(self, s, e, length):
+        ds = self.dataset
+        return ops.wave_view(ds.store, ds.row_off, ds.row_len, self._rows[s:e], self._crop[s:e], length, self.normalize)
 
 
 # ---- the option's wiring (core/algorithmbase.py) -----------------------------------------------------------------------------------------
@@ -223,8 +130,7 @@ def _is_audio_net(net):
 
 def refuse_unsupported(args):
     """The configurations the waveform loaders do not cover, each with its reason, decided from the yaml keys before any array is moved."""
-    if bool(getattr(args, "device_data", False)):
-        raise ValueError("device_audio and device_data are two input pipelines (waveforms / images): set one of them")
+    active_mode(args, "device_audio")
     net = getattr(args, "net", None)
     if net and not _is_audio_net(net):
         raise NotImplementedError("device_audio covers the usb_audio waveform pipelines only (ClassificationWave2Vec / HuBERT backbones): "
@@ -236,7 +142,7 @@ def refuse_unsupported(args):
     view_length(args)
 
 
-def refuse_unsupported_model(model):
+def refuse_unsupported_model(model, dataset_dict=None):
     """The same refusal for a builder handed in without a ``net`` name: decided from the model once it exists."""
     from ..nets.wave2vec import ClassificationWave2Vec
     if not isinstance(model, ClassificationWave2Vec):
@@ -290,19 +196,14 @@ def build_wave_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, nu
     """The loader_dict of AlgorithmBase.set_data_loader from resident datasets: train_lb (batch_size), train_ulb (batch_size * uratio),
     eval / test (eval_batch_size).  ``step_keys``: the parameter names of the algorithm's train_step -- a view it does not take is not made."""
     L = view_length(args)
-    strong = "x_ulb_s" in step_keys
-    if strong and dataset_dict["train_ulb"].n_variants == 0:
+    if "x_ulb_s" in step_keys and dataset_dict["train_ulb"].n_variants == 0:
         raise ValueError("device_audio: this algorithm's train_step takes x_ulb_s but the unlabelled set has no data_s; " + DATA_S_HELP)
     normalize = resolve_normalize(args, print_fn)
-    seed = int(getattr(args, "seed", 0) or 0)
-    per_epoch = num_train_iter // max(1, epochs)
-    ld = {}
-    for name, bs, keys in (("train_lb", args.batch_size, ("idx_lb", "x_lb", "y_lb")),
-                           ("train_ulb", args.batch_size * args.uratio, ("idx_ulb", "x_ulb_w", "x_ulb_s"))):
-        ds = dataset_dict[name]
-        sampler = EpochSampler(len(ds), per_epoch * bs * num_replicas, num_replicas, rank)     # one seed (the epoch) for both, as the reference
-        ld[name] = WaveTrainLoader(ds, bs, sampler, L, normalize, strong=strong, keys=keys, seed=(seed, rank, ROLES[name]))
-    for name in ("eval", "test"):
-        if dataset_dict.get(name) is not None:
-            ld[name] = WaveEvalLoader(dataset_dict[name], args.eval_batch_size, L, normalize)
-    return ld
+    return build_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank,
+                         lambda ds, bs, sampler, strong, keys, seed: WaveTrainLoader(ds, bs, sampler, L, normalize, strong=strong, keys=keys, seed=seed),
+                         lambda ds, bs: WaveEvalLoader(ds, bs, L, normalize))
+
+
+def eval_loader(args, dataset, batch_size, print_fn=print):
+    """The evaluation view of one resident dataset, as the 'eval' loader of build_wave_loaders makes it."""
+    return WaveEvalLoader(dataset, batch_size, view_length(args), resolve_normalize(args, print_fn))

@@ -13,6 +13,8 @@ import torch
 
 from .. import ops
 from .augment import GpuAugment
+from .modes import build_loaders
+from .ragged import EpochLoader
 
 # Normalize statistics of the reference's transforms (cv_datasets/cifar.py:16-21, stl10.py:16-18, eurosat.py:37-38)
 DATASET_STATS = {
@@ -92,30 +94,15 @@ class EpochSampler:
         return self.num_samples
 
 
-class DeviceTrainLoader:
+class DeviceTrainLoader(EpochLoader):
     """Per-step dicts of one epoch: consecutive ``batch_size`` chunks of the sampler's stream (drop_last).  ``keys`` name what a sample
     carries: 'idx_*' the dataset indices, 'y_*' the targets, 'x_*' a weak view and 'x_*_s' a strong view of the stored image -- every view an
     independent draw of ``aug`` (one srhip_augment launch).  ``strong=False`` leaves the strong views out: not drawn, not launched.
     The draws are a function of (``seed``, epoch): ``set_epoch`` / iterating again replays them."""
 
     def __init__(self, dataset, batch_size, sampler, aug, strong=True, keys=("idx_lb", "x_lb", "y_lb"), seed=(0,)):
-        self.dataset, self.batch_size, self.sampler, self.aug = dataset, int(batch_size), sampler, aug
-        self.keys = tuple(k for k in keys if strong or not self._is_strong(k))
-        if any(k.startswith("y") for k in self.keys) and dataset.targets is None:
-            raise ValueError("a loader with a target key needs a labelled dataset")
-        self.seed = tuple(int(s) for s in seed)
-        self.epoch = 0
-
-    @staticmethod
-    def _is_strong(k):
-        return k.startswith("x") and k.endswith("_s")
-
-    def set_epoch(self, epoch):
-        self.epoch = int(epoch)
-        self.sampler.set_epoch(epoch)
-
-    def __len__(self):
-        return len(self.sampler) // self.batch_size
+        super().__init__(dataset, batch_size, sampler, strong, keys, seed)
+        self.aug = aug
 
     def __iter__(self):
         self.sampler.set_epoch(self.epoch)
@@ -171,7 +158,7 @@ def refuse_unsupported(args):
         raise ValueError("device_data needs args.img_size (the training resolution every transform resizes to)")
 
 
-def refuse_unsupported_model(model):
+def refuse_unsupported_model(model, dataset_dict=None):
     """The same refusal for a builder handed in without a ``net`` name: decided from the model once it exists (the arrays are resident by then)."""
     from ..nets.wave2vec import ClassificationWave2Vec
     if getattr(model, "takes_tokens", False):
@@ -197,23 +184,19 @@ def build_device_datasets(args, dataset_dict, device):
     return {k: (None if v is None else DeviceImageDataset.from_reference(v, args.img_size, device)) for k, v in dataset_dict.items()}
 
 
-def build_device_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank):
+def build_device_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank, print_fn=print):
     """The loader_dict of AlgorithmBase.set_data_loader from resident datasets: train_lb (batch_size), train_ulb (batch_size * uratio),
     eval / test (eval_batch_size).  ``step_keys``: the parameter names of the algorithm's train_step -- a view it does not take is not made."""
     S = int(args.img_size)
     pad = int(S * (1 - getattr(args, "crop_ratio", 0.875)))          # RandomCrop(padding=...) of the transforms; train.py's default ratio
     mean, std = dataset_stats(args)
-    seed = int(getattr(args, "seed", 0) or 0)
-    per_epoch = num_train_iter // max(1, epochs)
-    ld = {}
-    for name, bs, keys in (("train_lb", args.batch_size, ("idx_lb", "x_lb", "y_lb")),
-                           ("train_ulb", args.batch_size * args.uratio, ("idx_ulb", "x_ulb_w", "x_ulb_s"))):
-        ds = dataset_dict[name]
-        sampler = EpochSampler(len(ds), per_epoch * bs * num_replicas, num_replicas, rank)     # one seed (the epoch) for both, as the reference
-        aug = GpuAugment(S, pad, mean, std, n_ops=3, device=ds.device)
-        ld[name] = DeviceTrainLoader(ds, bs, sampler, aug, strong="x_ulb_s" in step_keys, keys=keys, seed=(seed, rank, ROLES[name]))
-    for name in ("eval", "test"):
-        if dataset_dict.get(name) is not None:
-            ds = dataset_dict[name]
-            ld[name] = DeviceEvalLoader(ds, args.eval_batch_size, GpuAugment(S, 0, mean, std, device=ds.device))
-    return ld
+    return build_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank,
+                         lambda ds, bs, sampler, strong, keys, seed: DeviceTrainLoader(ds, bs, sampler, GpuAugment(S, pad, mean, std, n_ops=3, device=ds.device),
+                                                                                       strong=strong, keys=keys, seed=seed),
+                         lambda ds, bs: eval_loader(args, ds, bs))
+
+
+def eval_loader(args, dataset, batch_size, print_fn=print):
+    """transform_val over one resident dataset, as the 'eval' loader of build_device_loaders makes it."""
+    mean, std = dataset_stats(args)
+    return DeviceEvalLoader(dataset, batch_size, GpuAugment(int(args.img_size), 0, mean, std, device=dataset.device))

@@ -18,17 +18,14 @@ import numpy as np
 import torch
 
 from .. import ops
-from .device_loader import ROLES, EpochSampler
+from .device_loader import ROLES, EpochSampler             # noqa: F401  (re-exported beside the loaders they feed)
+from .modes import active_mode, build_loaders
+from .ragged import RaggedEvalLoader, RaggedStore, RaggedTrainLoader, _h2d, with_variants
 
 HUB_NAMES = {"bert_base_uncased": "bert-base-uncased", "bert_base_cased": "bert-base-cased"}     # the reference's collators (nlp_collactor.py:113-122)
 TOKENIZER_FILES = ("tokenizer.json", "vocab.txt")
 DATA_S_HELP = ("give the unlabelled set the augmented variants of every sentence as {'data': [...], 'data_s': [[variant 0 of every sentence], "
                "[variant 1 ...]]} (the reference's (ori, aug_0, aug_1) triples: its back-translations)")
-
-
-def _h2d(t, device):
-    """Every host-to-device copy of the loaders goes through here (one per epoch and train loader; the tests count them)."""
-    return t.to(device)
 
 
 def _rows(data, what, tokenize, max_length):
@@ -72,7 +69,7 @@ def _triples(data):
     return [str(t[0]) for t in rows], [[str(t[1 + v]) for t in rows] for v in range(2)]
 
 
-class DeviceTokenDataset:
+class DeviceTokenDataset(RaggedStore):
     """Token rows of any length in one flat int32 device array ``store``; row r occupies store[row_off[r] : row_off[r] + row_len[r]] and
     starts at a multiple of 4 ints (the gap holds ``pad_id``).  Rows 0 .. n - 1 are the sentences; with ``data_s`` (V lists of n variants)
     row n (1 + v) + i is variant v of sentence i (``strong_row``).  int64 targets resident too (None: unlabelled).  ``row_len_host`` /
@@ -83,38 +80,10 @@ class DeviceTokenDataset:
 
     def __init__(self, data, targets, device, data_s=None, max_length=None, tokenize=None):
         self.max_length = None if max_length is None else int(max_length)
-        rows = _rows(data, "data", tokenize, self.max_length)
-        self.n = len(rows)
-        if self.n == 0:
-            raise ValueError("device_tokens: the dataset holds no sentence")
-        self.n_variants = 0
-        if data_s is not None:
-            for v, var in enumerate(data_s):
-                var = _rows(var, "data_s[%d]" % v, tokenize, self.max_length)
-                if len(var) != self.n:
-                    raise ValueError("device_tokens: data_s[%d] must hold one variant of every sentence (%d), got %d" % (v, self.n, len(var)))
-                rows += var
-            self.n_variants = len(data_s)
-            if self.n_variants == 0:
-                raise ValueError("device_tokens: data_s is empty; " + DATA_S_HELP)
-        self.device = torch.device(device)
-        self.row_len_host = np.array([r.size for r in rows], dtype=np.int32)
-        padded = (self.row_len_host.astype(np.int64) + 3) & ~np.int64(3)
-        self.row_off_host = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
-        flat = np.full(int(padded.sum()), self.pad_id, dtype=np.int32)
-        for r, o in zip(rows, self.row_off_host):
-            flat[o:o + r.size] = r
+        rows, n, n_variants = with_variants(lambda d, what: _rows(d, what, tokenize, self.max_length), data, data_s,
+                                            "device_tokens", "sentence", DATA_S_HELP)
         self.max_id_host = int(max(int(r.max()) for r in rows))
-        self.store = torch.from_numpy(flat).to(self.device)
-        self.row_off = torch.from_numpy(self.row_off_host).to(self.device)
-        self.row_len = torch.from_numpy(self.row_len_host).to(self.device)
-        if targets is None:
-            self.targets = self.targets_host = None
-        else:
-            self.targets_host = np.asarray(targets.cpu() if torch.is_tensor(targets) else targets).astype(np.int64)
-            if self.targets_host.shape != (self.n,):
-                raise ValueError("targets must hold one label per sentence (%d sentences, targets of shape %s)" % (self.n, self.targets_host.shape))
-            self.targets = torch.from_numpy(self.targets_host).to(self.device)
+        super().__init__(rows, n, n_variants, targets, device, self.pad_id, "sentence")
 
     @classmethod
     def from_reference(cls, dset, device, tokenize=None, max_length=None):
@@ -124,21 +93,12 @@ class DeviceTokenDataset:
         as both augmentations (json_data.py:42): such variants are not stored."""
         if isinstance(dset, cls):
             return dset
-        if isinstance(dset, dict):
-            return cls(dset["data"], dset.get("targets"), device, dset.get("data_s"), max_length, tokenize)
-        ulb = bool(getattr(dset, "is_ulb", False))
-        data, data_s = list(dset.data), getattr(dset, "data_s", None)
-        tri = _triples(data)
+        data, targets, data_s = cls.reference_fields(dset)
+        tri = None if isinstance(dset, dict) else _triples(data)
         if tri is not None:
             data, var = tri
             data_s = None if all(x == "None" for v in var for x in v) else var
-        return cls(data, None if ulb else getattr(dset, "targets", None), device, data_s, max_length, tokenize)
-
-    def strong_row(self, variant, index):
-        return self.n * (1 + np.asarray(variant, dtype=np.int64)) + np.asarray(index, dtype=np.int64)
-
-    def __len__(self):
-        return self.n
+        return cls(data, targets, device, data_s, max_length, tokenize)
 
 
 def _view(ds, src_row, L):
@@ -146,7 +106,7 @@ def _view(ds, src_row, L):
     return TokenBatch(*ops.token_view(ds.store, ds.row_off, ds.row_len, src_row, L, ds.pad_id))
 
 
-class TokenTrainLoader:
+class TokenTrainLoader(RaggedTrainLoader):
     """Per-step dicts of one epoch: consecutive ``batch_size`` chunks of the sampler's stream (drop_last).  'idx_*' the dataset indices,
     'y_*' the targets, 'x_*' the sentence and 'x_*_s' one of its variants, picked uniformly -- every view a ``TokenBatch`` right-padded to
     the longest row of ITS OWN batch (the collator's ``padding=True``; the views of a step are NOT padded to a common length), one
@@ -155,81 +115,28 @@ class TokenTrainLoader:
     goes to the device in ONE copy when the epoch starts; the per-batch lengths are computed on the host from ``row_len_host`` (vectorised;
     nothing is read back from the device).  ``draws`` keeps the host arrays of the last epoch started:
     {view key: (store rows int64 [N], padded length of every batch int64 [len(self)])}."""
+    mode_key, data_s_help = "device_tokens", DATA_S_HELP
 
-    def __init__(self, dataset, batch_size, sampler, strong=True, keys=("idx_lb", "x_lb", "y_lb"), seed=(0,)):
-        self.dataset, self.batch_size, self.sampler = dataset, int(batch_size), sampler
-        self.keys = tuple(k for k in keys if strong or not self._is_strong(k))
-        if any(k.startswith("y") for k in self.keys) and dataset.targets is None:
-            raise ValueError("a loader with a target key needs a labelled dataset")
-        if any(self._is_strong(k) for k in self.keys) and dataset.n_variants == 0:
-            raise ValueError("device_tokens: a strong view was asked of a dataset without data_s; " + DATA_S_HELP)
-        self.seed = tuple(int(s) for s in seed)
-        self.epoch = 0
-        self.draws = {}
+    def _copy(self, table):
+        return _h2d(table, self.dataset.device)
 
-    @staticmethod
-    def _is_strong(k):
-        return k.startswith("x") and k.endswith("_s")
+    def _draw(self, rng, key, src):
+        """No table row beyond the store rows; the padded length of every batch comes from the host's copy of the row lengths."""
+        lens, B, nb = self.dataset.row_len_host, self.batch_size, len(self)
+        ops.check_token_rows(src, lens)
+        return [], (src, lens[src[:nb * B]].reshape(nb, B).max(axis=1).astype(np.int64))
 
-    def set_epoch(self, epoch):
-        self.epoch = int(epoch)
-        self.sampler.set_epoch(epoch)
-
-    def __len__(self):
-        return len(self.sampler) // self.batch_size
-
-    def _epoch_table(self):
-        """The epoch as one int64 host table [rows, N] and the meaning of its rows: {key: row} ('idx' / 'y': the values; views: the store rows)."""
-        ds, B, nb = self.dataset, self.batch_size, len(self)
-        self.sampler.set_epoch(self.epoch)
-        rng = np.random.Generator(np.random.PCG64(self.seed + (self.epoch,)))
-        stream = np.ascontiguousarray(self.sampler.indices(), dtype=np.int64)
-        N, rows, where, self.draws = stream.size, [], {}, {}
-        for k in self.keys:
-            where[k] = len(rows)
-            if k.startswith("idx"):
-                rows.append(stream)
-            elif k.startswith("y"):
-                rows.append(ds.targets_host[stream])
-            else:
-                src = ds.strong_row(rng.integers(0, ds.n_variants, size=N), stream) if self._is_strong(k) else stream
-                ops.check_token_rows(src, ds.row_len_host)
-                rows.append(src)
-                self.draws[k] = (src, ds.row_len_host[src[:nb * B]].reshape(nb, B).max(axis=1).astype(np.int64))
-        return np.stack(rows), where, N
-
-    def __iter__(self):
-        ds, B = self.dataset, self.batch_size
-        table, where, N = self._epoch_table()
-        dev = _h2d(torch.from_numpy(table), ds.device)                                     # the epoch's one copy, sliced per step
-        lengths = {k: v[1].tolist() for k, v in self.draws.items()}
-        for t in range(len(self)):
-            s = t * B
-            yield {k: (_view(ds, dev[where[k], s:s + B], lengths[k][t]) if k in lengths else dev[where[k], s:s + B]) for k in self.keys}
+    def _view_fn(self, dev, row, draw):
+        ds, B, src, lengths = self.dataset, self.batch_size, dev[row], draw[1].tolist()
+        return lambda s, t: _view(ds, src[s:s + B], lengths[t])
 
 
-class TokenEvalLoader:
+class TokenEvalLoader(RaggedEvalLoader):
     """The dataset in order, last partial batch kept: {'x_lb': TokenBatch, 'y_lb'}, every batch right-padded to its own longest row -- the
     reference's evaluation collator.  The host knows the lengths: no synchronisation and no host-to-device copy."""
 
-    def __init__(self, dataset, batch_size):
-        if dataset.targets is None:
-            raise ValueError("the evaluation loader needs a labelled dataset")
-        self.dataset, self.batch_size = dataset, int(batch_size)
-        self._rows = torch.arange(len(dataset), dtype=torch.int64, device=dataset.device)          # made on the device: nothing to copy
-
-    def __len__(self):
-        return -(-len(self.dataset) // self.batch_size)
-
-    def batch_lengths(self):
-        ds, n = self.dataset, len(self.dataset)
-        return [int(ds.row_len_host[s:min(s + self.batch_size, n)].max()) for s in range(0, n, self.batch_size)]
-
-    def __iter__(self):
-        ds, n = self.dataset, len(self.dataset)
-        for s, L in zip(range(0, n, self.batch_size), self.batch_lengths()):
-            e = min(s + self.batch_size, n)
-            yield {"x_lb": _view(ds, self._rows[s:e], L), "y_lb": ds.targets[s:e]}
+    def _view(self, s, e, length):
+        return _view(self.dataset, self._rows[s:e], length)
 
 
 # ---- the tokenizer (needed only when a dataset holds strings) ----------------------------------------------------------------------------
@@ -271,10 +178,8 @@ def _is_token_net(net):
 
 def refuse_unsupported(args):
     """The configurations the token loaders do not cover, each with its reason, decided from the yaml keys before any array is moved."""
-    for other, what in (("device_data", "images"), ("device_audio", "waveforms")):
-        if bool(getattr(args, other, False)):
-            raise ValueError("device_tokens and %s are two input pipelines (token batches / %s): set one of them" % (other, what))
-    net = getattr(args, "net", None)
+    active_mode(args, "device_tokens")
+    net =getattr(args, "net", None)
     if net and not _is_token_net(net):
         raise NotImplementedError("device_tokens covers the usb_nlp token pipelines only (ClassificationBert backbones): net %r does not take "
                                   "token batches" % (net,))
@@ -327,25 +232,18 @@ def build_token_datasets(args, dataset_dict, device):
     return {k: (None if v is None else DeviceTokenDataset.from_reference(v, device, tokenize, max_length)) for k, v in dataset_dict.items()}
 
 
-def build_token_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank):
+def build_token_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank, print_fn=print):
     """The loader_dict of AlgorithmBase.set_data_loader from resident datasets: train_lb (batch_size), train_ulb (batch_size * uratio),
     eval / test (eval_batch_size).  ``step_keys``: the parameter names of the algorithm's train_step -- a view it does not take is not made."""
-    strong = "x_ulb_s" in step_keys
     for name in ("train_lb", "train_ulb"):
         if dataset_dict.get(name) is None:
             raise ValueError("device_tokens: dataset_dict[%r] is missing or None; the train loaders need a labelled and an unlabelled set (every "
                              "train_step of this project takes x_lb and x_ulb_w)" % name)
-    if strong and dataset_dict["train_ulb"].n_variants == 0:
+    if "x_ulb_s" in step_keys and dataset_dict["train_ulb"].n_variants == 0:
         raise ValueError("device_tokens: this algorithm's train_step takes x_ulb_s but the unlabelled set has no data_s; " + DATA_S_HELP)
-    seed = int(getattr(args, "seed", 0) or 0)
-    per_epoch = num_train_iter // max(1, epochs)
-    ld = {}
-    for name, bs, keys in (("train_lb", args.batch_size, ("idx_lb", "x_lb", "y_lb")),
-                           ("train_ulb", args.batch_size * args.uratio, ("idx_ulb", "x_ulb_w", "x_ulb_s"))):
-        ds = dataset_dict[name]
-        sampler = EpochSampler(len(ds), per_epoch * bs * num_replicas, num_replicas, rank)     # one seed (the epoch) for both, as the reference
-        ld[name] = TokenTrainLoader(ds, bs, sampler, strong=strong, keys=keys, seed=(seed, rank, ROLES[name]))
-    for name in ("eval", "test"):
-        if dataset_dict.get(name) is not None:
-            ld[name] = TokenEvalLoader(dataset_dict[name], args.eval_batch_size)
-    return ld
+    return build_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank, TokenTrainLoader, TokenEvalLoader)
+
+
+def eval_loader(args, dataset, batch_size, print_fn=print):
+    """The evaluation view of one resident dataset, as the 'eval' loader of build_token_loaders makes it."""
+    return TokenEvalLoader(dataset, batch_size)
