@@ -6,10 +6,13 @@ crop, zero padding, the feature extractor's normalisation -- is one launch (data
 ``alg.evaluate()`` run with no hand-written batch generator.
 
 SRFreeMatch takes a strong view: the unlabelled set carries V = 2 pre-augmented variants of every clip (``data_s``), here a numpy stand-in for the
-reference's sox chain (gain, a speed change by resampling, additive noise).
+reference's sox chain (gain, a speed change by resampling, additive noise).  With ``--device-strong`` (``device_audio_strong: True``) there is no
+``data_s``: SRFlexMatch trains on strong views the engine makes on the device from the clean clips, two freshly drawn effects per sample and epoch
+(csrc/wave_strong.hip).
 
     python examples/train_device_audio.py --steps 60
     python examples/train_device_audio.py --steps 60 --algorithm srfreematch
+    python examples/train_device_audio.py --steps 60 --device-strong  # srflexmatch, the strong views made on the device
     python examples/train_device_audio.py --steps 60 --run-hooks     # the reference's evaluation / checkpoint / logging hooks drive the run
 """
 import argparse
@@ -58,6 +61,7 @@ class PrintHook(Hook):
 
 
 ALGORITHMS = {"srpseudolabel": dict(unsup_warm_up=0.4),
+              "srflexmatch": dict(thresh_warmup=True),
               "srfreematch": dict(ema_p=0.9, use_quantile=True, clip_thresh=False, ent_loss_ratio=0.01)}
 
 
@@ -70,13 +74,17 @@ def main():
     ap.add_argument("--algorithm", choices=sorted(ALGORITHMS), default="srpseudolabel")
     ap.add_argument("--run-hooks", action="store_true",
                     help="run_hooks + device_eval: evaluate and checkpoint every 20 steps (into a temporary save_dir), log every 10")
+    ap.add_argument("--device-strong", action="store_true",
+                    help="device_audio_strong: the strong views are made on the device, no data_s (srflexmatch unless --algorithm names a strong-view one)")
     a = ap.parse_args()
+    if a.device_strong and a.algorithm == "srpseudolabel":
+        a.algorithm = "srflexmatch"
     C = a.classes
     x_lb, y_lb = synth_clips(10 * C, C, 1)
     x_ulb, _ = synth_clips(512, C, 2)
     x_te, y_te = synth_clips(128, C, 3)
     ulb = {"data": x_ulb, "targets": None}
-    if a.algorithm == "srfreematch":                          # its train_step takes x_ulb_s: V = 2 pre-augmented variants per clip
+    if a.algorithm != "srpseudolabel" and not a.device_strong:   # its train_step takes x_ulb_s: V = 2 pre-augmented variants per clip
         rng = np.random.Generator(np.random.PCG64(4))
         ulb["data_s"] = [[strong_variant(w, rng) for w in x_ulb] for _ in range(2)]
     steps = max(a.steps, a.epochs) // a.epochs * a.epochs
@@ -86,7 +94,7 @@ def main():
         feature_dim=128, sr_lr=5e-4, sr_ema=False, sr_ema_m=0.99, gpu=0, rank=0, world_size=1, distributed=False, seed=0,
         # the input pipeline: what a usb_audio yaml says (window, rate, batch sizes, sampler) + the clips + the option
         dataset="synthetic_tones", sample_rate=RATE, max_length_seconds=SECONDS, batch_size=a.batch, uratio=1, eval_batch_size=16,
-        train_sampler="RandomSampler", device_audio=True, audio_do_normalize=True,
+        train_sampler="RandomSampler", device_audio=True, audio_do_normalize=True, device_audio_strong=a.device_strong,
         dataset_dict={"train_lb": {"data": x_lb, "targets": y_lb}, "train_ulb": ulb, "eval": {"data": x_te, "targets": y_te}},
         **ALGORITHMS[a.algorithm])
     if a.run_hooks:

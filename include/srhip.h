@@ -830,6 +830,38 @@ int srhip_resize_bilinear_u8(const unsigned char* src, int N, int H0, int W0, un
 int srhip_wave_view(const float* store, const long long* row_off, const int* row_len, int n_rows, const long long* src_row,
                     const int* crop_off, int B, int S, int normalize, float* out, int ldo, void* stream);
 
+/* ---- one effect slot of the device-made strong waveform view (``device_audio_strong: True``, semireward_amd/data/device_audio.py,
+ * csrc/wave_strong.hip).  The chain is the engine's own (tests/_wave_strong_cases.py restates it in float64 numpy and is its specification):
+ * it keeps the structure and the draw distributions of the reference's WaveformTransforms (datasetbase.py:12-39), not sox's filters.
+ * Addressing as srhip_wave_view: with r = src_row[b], the source is the n = row_len[r] floats at store + row_off[r] (slot 0: the resident clip
+ * store; a later slot: the scratch rows the previous slot wrote).  Output row b is dst + b * pitch (fp32, 16-byte aligned, pitch % 4 == 0); the
+ * kernel writes exactly dst_len[b] floats of it and nothing else.  op / param / dst_len are DEVICE arrays [B]; host_op / host_param /
+ * host_dst_len are the HOST arrays they were copied from, which the entry checks before it launches (the device arrays ride in a loader's one
+ * copy per epoch; the kernel writes nothing for a row whose device values the entry would have refused).
+ *   SR_WAVE_COPY      out = x, m = n
+ *   SR_WAVE_GAIN      param = the fp32 bits of g = 10^(att / 20): out = clamp(x * (g / max |x|), -1, 1), m = n (sox ``gain -n``); an all-zero row is
+ *                     copied.  The maximum is exact; an element is the fp32 rounding of the fp64 product x * (g / peak).
+ *   SR_WAVE_RESAMPLE  param = step = round(s * 2^32), 2^31 <= step <= 2^33 (speed: s = speed; pitch: s = 2^(cents / 1200), a resample, not
+ *                     WSOLA).  m = max(1, (n << 32) / step).  Output j sits at p = j * step (64-bit integers): i0 = p >> 32,
+ *                     f = (p & 0xffffffff) 2^-32; c = min(1, 2^32 / step), T = 16 / c;  out[j] = sum_k x[k] h(i0 + f - k) over the integers k of
+ *                     [0, n - 1] with |i0 + f - k| < T, k ascending, h(u) = c sinc(c u) (0.5 + 0.5 cos(pi u / T)), weights and sum in fp32, no
+ *                     renormalisation at the edges.  step == 2^32 copies bit for bit.
+ *   SR_WAVE_REVERB    Freeverb (public domain), mono, wet only, empty state, the tail past n dropped, m = n: in = 0.015 x; eight parallel combs
+ *                     (y = buf[idx]; st = 0.8 y + 0.2 st; buf[idx] = in + 0.84 st) summed in comb order; four series allpasses
+ *                     (b = buf[idx]; out = b - in; buf[idx] = in + 0.5 b); out * 3.  delays12: HOST pointer to the eight comb and four allpass
+ *                     delays in samples (max(1, round(d * sample_rate / 44100)), d = 1116 1188 1277 1356 1422 1491 1557 1617 / 556 441 341 225),
+ *                     passed to the kernel by value.  Evaluated in chunks of the shortest delay with the damping recursion as its first 24 terms
+ *                     (the remainder is below 0.2^24 of the signal); delay lines in LDS.
+ * One 1024-thread workgroup per row, rows of different ops share the launch; no atomics, fixed summation order (run-to-run bit-identical).
+ * SR_EINVAL: a null pointer, n_rows <= 0, B <= 0, B > 65535, pitch <= 0, pitch % 4, dst not 16-byte aligned, a host_op outside 0..3, a
+ * host_dst_len <= 0 or above pitch, a resample step outside [2^31, 2^33], a delay <= 0, delays whose lines (sum of the comb delays + 8 (23 + C) +
+ * sum of the allpass delays + 4 C + 16 C floats, C the shortest delay) do not fit 64 KiB - 256 B of LDS, a shortest delay above 256.  The Python wrapper also checks the rows
+ * and lengths against the store, dst_len against the op's length rule and that source and destination are different buffers. */
+enum { SR_WAVE_COPY = 0, SR_WAVE_GAIN = 1, SR_WAVE_RESAMPLE = 2, SR_WAVE_REVERB = 3 };
+int srhip_wave_effect(const float* store, const long long* row_off, const int* row_len, int n_rows, const long long* src_row, const int* op,
+                      const long long* param, const int* dst_len, int B, float* dst, int pitch, const int* host_op, const long long* host_param,
+                      const int* host_dst_len, const int* delays12, void* stream);
+
 /* ---- one view of a token batch from the device-resident token store (``device_tokens: True``, semireward_amd/data/device_tokens.py): the
  * collator's ``tokenizer.pad(padding=True)`` (nlp_collactor.py:63-110) on rows tokenised once, and the lengths srhip_mask_lengths would
  * recover from its attention mask, one launch.

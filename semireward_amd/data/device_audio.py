@@ -13,8 +13,13 @@ with the reference's unseeded draws (``random.randint`` in every worker process)
   * every training view is padded to L = int(round(sample_rate * max_length_seconds)) samples.  The reference pads x_lb / x_ulb_w to the
     batch's own longest row and only the strong view to L; the step concatenates the three views, so they need one length.  The two agree
     whenever a batch holds a clip of at least L samples.
-  * the strong view is a crop of a PRE-AUGMENTED variant of the clip (``data_s``).  The reference runs a random sox effect chain on the CPU
-    (torchaudio.sox_effects, unseeded): it can be neither restated on the device nor pinned by a fixture."""
+  * the strong view is a crop of a PRE-AUGMENTED variant of the clip (``data_s``), or -- ``device_audio_strong: True`` -- of the clip after two
+    effects made on the device (srhip_wave_effect, csrc/wave_strong.hip), drawn afresh per sample and epoch.  The reference runs a random sox
+    effect chain on the CPU (torchaudio.sox_effects, unseeded): sox's filters can be neither restated on the device nor pinned by a fixture.
+    The device chain keeps the reference's structure and draw distributions (``draw_effects``: two of gain / pitch / speed / reverb with
+    replacement, applied to the whole clip before the crop) with filters of the engine's own: a peak-normalising gain, one windowed-sinc
+    resampler for speed and pitch (pitch changes the length by at most 0.12 %, sox keeps it by WSOLA), Freeverb.  Effects run one after the
+    other at the clip's own rate; a clip shorter than the shortest comb delay leaves the reverb as silence."""
 import json
 import os
 
@@ -68,6 +73,32 @@ class DeviceWaveDataset(RaggedStore):
         return cls(data, targets, device, data_s)
 
 
+STRONG_KEY = "device_audio_strong"
+MAX_GROWTH = 4                    # two slots, each at most doubles a clip (speed 0.5)
+MAX_VIEW_SOURCE = 1 << 30         # the longest row srhip_wave_effect / srhip_wave_view address
+EFFECTS = ("gain", "pitch", "speed", "reverb")                 # the reference's effects_list, in its order
+
+
+def draw_effects(rng, n0):
+    """The strong view's draws for clips of ``n0`` samples, the reference's rule (datasetbase.py:14-27) from ``rng``: per sample three uniforms,
+    always drawn -- speed = 0.5 + 1.5 u, cents = -2 + 4 u, att = int(-5 + 10 u), truncated toward zero: an integer in -4 .. 4 -- then two effects
+    uniform on 0 .. 3 with replacement (``random.choices(effects_list, k=2)``).  Returned with what srhip_wave_effect is given for them
+    ('op', 'param': gain -> the fp32 bits of 10^(att / 20); pitch and speed -> the 32.32 fixed-point step round(s 2^32) with s = 2^(cents / 1200)
+    and s = speed; reverb -> 0) and the length chain 'lens' [N, 3] by the kernel's integer rule (ops.wave_effect_len)."""
+    n0 = np.asarray(n0, dtype=np.int64)
+    u = rng.random((n0.size, 3))
+    effect = rng.integers(0, 4, size=(n0.size, 2))
+    speed, cents = 0.5 + 1.5 * u[:, 0], -2.0 + 4.0 * u[:, 1]
+    att = np.clip(np.trunc(-5.0 + 10.0 * u[:, 2]), -4, 4).astype(np.int64)              # (u = 0 exactly would give -5: kept inside the stated range)
+    gain = np.asarray(10.0 ** (att / 20.0), dtype=np.float32).view(np.uint32).astype(np.int64)
+    step_pitch, step_speed = (np.floor(s * float(ops.WAVE_STEP_ONE) + 0.5).astype(np.int64) for s in (2.0 ** (cents / 1200.0), speed))
+    op = np.array([ops.WAVE_GAIN, ops.WAVE_RESAMPLE, ops.WAVE_RESAMPLE, ops.WAVE_REVERB], dtype=np.int32)[effect]
+    param = np.stack([gain, step_pitch, step_speed, np.zeros_like(gain)], axis=1)[np.arange(n0.size)[:, None], effect]
+    n1 = ops.wave_effect_len(n0, op[:, 0], param[:, 0])
+    n2 = ops.wave_effect_len(n1, op[:, 1], param[:, 1])
+    return dict(speed=speed, cents=cents, att=att, effect=effect, op=op, param=param, lens=np.stack([n0, n1, n2], axis=1))
+
+
 def crop_offsets(rng, lens, L):
     """random_subsample's offset for clips of ``lens`` samples: 0 when len <= L, else uniform on [0, len - L - 1], both ends included."""
     lens = np.asarray(lens, dtype=np.int64)
@@ -81,30 +112,87 @@ class WaveTrainLoader(RaggedTrainLoader):
     [batch_size, L], one srhip_wave_view launch.  ``strong=False`` leaves the strong views out: not drawn, not launched.  The draws are a
     function of (``seed``, epoch): ``set_epoch`` / iterating again replays them.  Everything an epoch needs -- its index stream, targets, store
     rows and crop offsets -- goes to the device in ONE copy when the epoch starts; ``draws`` keeps the host arrays of the last epoch started:
-    {view key: (store rows int64 [N], crop offsets int32 [N])}."""
+    {view key: (store rows int64 [N], crop offsets int32 [N])}.
+
+    ``device_strong=True`` (``device_audio_strong``): 'x_*_s' is made on the device from the CLEAN clip instead -- two effects drawn per sample
+    and epoch (``draw_effects``), two srhip_wave_effect launches through two scratch buffers [batch_size, pitch] allocated once, then the crop
+    of the augmented clip by srhip_wave_view: three launches, no host synchronisation, no allocation besides the view.  The effect draws ride
+    behind the view's rows in the same one copy and are drawn last, so every other view is what it is without the option.  ``strong_draws``
+    keeps them for the last epoch started: 'speed' / 'cents' / 'att' [N], 'effect' [N, 2] (0 gain, 1 pitch, 2 speed, 3 reverb), 'op' int32
+    [N, 2] and 'param' int64 [N, 2] (what srhip_wave_effect is given), 'lens' int64 [N, 3] (the clip, after slot 0, after slot 1)."""
     mode_key, data_s_help = "device_audio", DATA_S_HELP
 
-    def __init__(self, dataset, batch_size, sampler, L, normalize=True, strong=True, keys=("idx_lb", "x_lb", "y_lb"), seed=(0,)):
-        self.L, self.normalize = int(L), bool(normalize)
+    def __init__(self, dataset, batch_size, sampler, L, normalize=True, strong=True, keys=("idx_lb", "x_lb", "y_lb"), seed=(0,), device_strong=False,
+                 sample_rate=None):
+        self.L, self.normalize, self.makes_strong = int(L), bool(normalize), bool(device_strong)
         super().__init__(dataset, batch_size, sampler, strong, keys, seed)
+        self.strong_draws = None
+        if self.makes_strong and any(self._is_strong(k) for k in self.keys):
+            if dataset.n_variants:
+                raise ValueError("%s: the unlabelled set carries data_s (pre-augmented variants) and the strong view is to be made on the device: "
+                                 "there must be one source of strong views -- drop data_s or the key" % STRONG_KEY)
+            if not sample_rate or sample_rate <= 0:
+                raise ValueError("%s needs the clips' sample_rate (the reverb's delays are set in samples)" % STRONG_KEY)
+            longest = int(dataset.row_len_host.argmax())
+            self.pitch = (MAX_GROWTH * int(dataset.row_len_host[longest]) + 3) & ~3        # each slot at most doubles a clip (speed 0.5)
+            if self.pitch > MAX_VIEW_SOURCE:
+                raise ValueError("%s: clip %d holds %d samples; after two effects it may hold %d times as many, beyond the 2^30 samples "
+                                 "srhip_wave_view addresses" % (STRONG_KEY, longest, dataset.row_len_host[longest], MAX_GROWTH))
+            dev, B = dataset.device, self.batch_size
+            self.delays = ops.reverb_delays(sample_rate)
+            self._scratch = [torch.empty(B, self.pitch, dtype=torch.float32, device=dev) for _ in range(2)]
+            self._rows = torch.arange(B, dtype=torch.int64, device=dev)                    # a scratch row per batch row ...
+            self._scratch_off = self._rows * self.pitch                                     # ... at a fixed pitch
 
     def _copy(self, table):
         return _h2d(table, self.dataset.device)
 
     def _draw(self, rng, key, src):
-        """One more table row behind the store rows: its first N int32 are the crop offsets."""
+        """One more table row behind the store rows: its first N int32 are the crop offsets.  A device-made strong view adds its effects:
+        [crop | op 0], [op 1 | length after slot 0], [length after slot 1 | -], param 0, param 1."""
         lens = self.dataset.row_len_host
-        crop = crop_offsets(rng, lens[src], self.L)
-        ops.check_wave_rows(src, crop, lens)
-        packed = np.zeros(src.size, dtype=np.int64)
-        packed.view(np.int32)[:src.size] = crop
-        return [packed], (src, crop)
+        made = self.makes_strong and self._is_strong(key)
+        if made:
+            self.strong_draws = draw_effects(rng, lens[src])
+            op, param, chain = (self.strong_draws[k] for k in ("op", "param", "lens"))
+            crop = crop_offsets(rng, chain[:, 2], self.L)
+            ops.check_wave_rows(np.arange(src.size), crop, chain[:, 2])
+            ops.check_wave_rows(src, np.zeros_like(crop), lens)
+        else:
+            crop = crop_offsets(rng, lens[src], self.L)
+            ops.check_wave_rows(src, crop, lens)
 
-    def _view_fn(self, dev, row, draw):
+        def pack(lo, hi=None):
+            packed = np.zeros(src.size, dtype=np.int64)
+            packed.view(np.int32)[:src.size] = lo
+            if hi is not None:
+                packed.view(np.int32)[src.size:] = hi
+            return packed
+        if not made:
+            return [pack(crop)], (src, crop)
+        return [pack(crop, op[:, 0]), pack(op[:, 1], chain[:, 1]), pack(chain[:, 2]), param[:, 0].copy(), param[:, 1].copy()], (src, crop)
+
+    def _view_fn(self, dev, row, draw, key):
         ds, B, L, normalize, wave_view = self.dataset, self.batch_size, self.L, self.normalize, ops.wave_view
         store, row_off, row_len = ds.store, ds.row_off, ds.row_len
-        src, crop = dev[row], dev.view(torch.int32)[row + 1]                               # (as int32 the table is [rows, 2 N]: the crop offsets are the first N)
-        return lambda s, t: wave_view(store, row_off, row_len, src[s:s + B], crop[s:s + B], L, normalize)
+        i32, N = dev.view(torch.int32), dev.shape[1]                                         # (as int32 the table is [rows, 2 N]: two arrays of N a row)
+        src, crop = dev[row], i32[row + 1]
+        if not (self.makes_strong and self._is_strong(key)):
+            return lambda s, t: wave_view(store, row_off, row_len, src[s:s + B], crop[s:s + B], L, normalize)
+        wave_effect, (a, b), rows, off, delays = ops.wave_effect, self._scratch, self._rows, self._scratch_off, self.delays
+        op0, op1, len1, len2, par0, par1 = i32[row + 1][N:], i32[row + 2], i32[row + 2][N:], i32[row + 3], dev[row + 4], dev[row + 5]
+        sd, h_src, h_len, h_rows = self.strong_draws, draw[0], ds.row_len_host, np.arange(B)      # the host arrays the entry checks: cut once per epoch
+        (h_op0, h_op1), (h_par0, h_par1) = (np.ascontiguousarray(sd[k].T) for k in ("op", "param"))
+        _, h_len1, h_len2 = np.ascontiguousarray(sd["lens"].T.astype(np.int32))
+
+        def view(s, t):
+            e = s + B
+            wave_effect(store, row_off, row_len, src[s:e], op0[s:e], par0[s:e], len1[s:e], a, delays,
+                        host=(h_src[s:e], h_op0[s:e], h_par0[s:e], h_len1[s:e], h_len))
+            wave_effect(a, off, len1[s:e], rows, op1[s:e], par1[s:e], len2[s:e], b, delays,
+                        host=(h_rows, h_op1[s:e], h_par1[s:e], h_len2[s:e], h_len1[s:e]))
+            return wave_view(b, off, len2[s:e], rows, crop[s:e], L, normalize)
+        return view
 
 
 class WaveEvalLoader(RaggedEvalLoader):
@@ -140,6 +228,15 @@ def refuse_unsupported(args):
         raise NotImplementedError("device_audio: train_sampler %r is not supported (only 'RandomSampler', the reference's DistributedSampler "
                                   "index stream, is restated on the device path)" % (sampler,))
     view_length(args)
+    device_strong(args)
+
+
+def device_strong(args):
+    """Whether ``device_audio_strong`` is on -- refused without ``device_audio``, whose resident clip store it reads."""
+    on = bool(getattr(args, STRONG_KEY, False))
+    if on and not getattr(args, "device_audio", False):
+        raise ValueError("%s: True makes the strong waveform view on the device from the resident clip store: it needs device_audio: True" % STRONG_KEY)
+    return on
 
 
 def refuse_unsupported_model(model, dataset_dict=None):
@@ -196,11 +293,17 @@ def build_wave_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, nu
     """The loader_dict of AlgorithmBase.set_data_loader from resident datasets: train_lb (batch_size), train_ulb (batch_size * uratio),
     eval / test (eval_batch_size).  ``step_keys``: the parameter names of the algorithm's train_step -- a view it does not take is not made."""
     L = view_length(args)
-    if "x_ulb_s" in step_keys and dataset_dict["train_ulb"].n_variants == 0:
+    made = device_strong(args)
+    if made and dataset_dict["train_ulb"].n_variants:
+        raise ValueError("%s: the unlabelled set carries data_s (pre-augmented variants) and the key asks for strong views made on the device: "
+                         "there must be one source of strong views -- drop data_s or the key" % STRONG_KEY)
+    if "x_ulb_s" in step_keys and dataset_dict["train_ulb"].n_variants == 0 and not made:
         raise ValueError("device_audio: this algorithm's train_step takes x_ulb_s but the unlabelled set has no data_s; " + DATA_S_HELP)
     normalize = resolve_normalize(args, print_fn)
+    sr = getattr(args, "sample_rate", None)
     return build_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank,
-                         lambda ds, bs, sampler, strong, keys, seed: WaveTrainLoader(ds, bs, sampler, L, normalize, strong=strong, keys=keys, seed=seed),
+                         lambda ds, bs, sampler, strong, keys, seed: WaveTrainLoader(ds, bs, sampler, L, normalize, strong=strong, keys=keys, seed=seed,
+                                                                                     device_strong=made, sample_rate=sr),
                          lambda ds, bs: WaveEvalLoader(ds, bs, L, normalize))
 
 

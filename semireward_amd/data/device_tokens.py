@@ -126,7 +126,7 @@ class TokenTrainLoader(RaggedTrainLoader):
         ops.check_token_rows(src, lens)
         return [], (src, lens[src[:nb * B]].reshape(nb, B).max(axis=1).astype(np.int64))
 
-    def _view_fn(self, dev, row, draw):
+    def _view_fn(self, dev, row, draw, key):
         ds, B, src, lengths = self.dataset, self.batch_size, dev[row], draw[1].tolist()
         return lambda s, t: _view(ds, src[s:s + B], lengths[t])
 

@@ -100,11 +100,13 @@ class RaggedTrainLoader(EpochLoader):
     """Everything an epoch needs -- its index stream, targets, the store rows of every view and what ``_draw`` adds -- goes to the device in ONE
     copy when the epoch starts, sliced per step; a view is one launch.  A strong view reads one of the row's variants, picked uniformly.
     ``draws`` keeps the host arrays of the last epoch started, {view key: (store rows int64 [N], the mode's second array)}.
-    A mode sets ``mode_key`` / ``data_s_help`` (its messages) and the two hooks ``_draw`` and ``_view_fn``."""
+    A mode sets ``mode_key`` / ``data_s_help`` (its messages) and the two hooks ``_draw`` and ``_view_fn``.  A loader whose ``makes_strong`` is
+    set makes its strong view itself, from the clean row: no variant is drawn and none is needed, the strong key's store rows are the stream."""
+    makes_strong = False
 
     def __init__(self, dataset, batch_size, sampler, strong=True, keys=("idx_lb", "x_lb", "y_lb"), seed=(0,)):
         super().__init__(dataset, batch_size, sampler, strong, keys, seed)
-        if any(self._is_strong(k) for k in self.keys) and dataset.n_variants == 0:
+        if any(self._is_strong(k) for k in self.keys) and dataset.n_variants == 0 and not self.makes_strong:
             raise ValueError("%s: a strong view was asked of a dataset without data_s; %s" % (self.mode_key, self.data_s_help))
         self.draws = {}
 
@@ -112,8 +114,8 @@ class RaggedTrainLoader(EpochLoader):
         """(the table rows a view adds behind its store rows ``src``, draws[key]); draws from ``rng`` and checks the rows on the host."""
         raise NotImplementedError
 
-    def _view_fn(self, dev, row, draw):
-        """f(s, t) -> the view of step t (stream positions s .. s + batch_size) from the device table, whose ``row`` holds the store rows."""
+    def _view_fn(self, dev, row, draw, key):
+        """f(s, t) -> the view ``key`` of step t (stream positions s .. s + batch_size) from the device table, whose ``row`` holds the store rows."""
         raise NotImplementedError
 
     def _copy(self, table):
@@ -136,7 +138,8 @@ class RaggedTrainLoader(EpochLoader):
             elif k.startswith("y"):
                 rows.append(ds.targets_host[stream])
             else:
-                src = ds.strong_row(rng.integers(0, ds.n_variants, size=N), stream) if self._is_strong(k) else stream
+                variant = self._is_strong(k) and not self.makes_strong
+                src = ds.strong_row(rng.integers(0, ds.n_variants, size=N), stream) if variant else stream
                 extra, self.draws[k] = self._draw(rng, k, src)
                 rows += [src] + extra
         return np.stack(rows), where, N
@@ -145,7 +148,7 @@ class RaggedTrainLoader(EpochLoader):
         B = self.batch_size
         table, where, N = self._epoch_table()
         dev = self._copy(torch.from_numpy(table))                                          # the epoch's one copy, sliced per step
-        cols = [(k, None, self._view_fn(dev, where[k], self.draws[k])) if k in self.draws else (k, dev[where[k]], None) for k in self.keys]
+        cols = [(k, None, self._view_fn(dev, where[k], self.draws[k], k)) if k in self.draws else (k, dev[where[k]], None) for k in self.keys]
         for t in range(len(self)):
             s, out = t * B, {}
             for k, col, view in cols:                                                      # (the rows are cut once per epoch: a step only slices)

@@ -1636,6 +1636,86 @@ def wave_view(store, row_off, row_len, src_row, crop_off, S, normalize, host=Non
     return out if ldo == S else out[:, :S]
 
 
+WAVE_COPY, WAVE_GAIN, WAVE_RESAMPLE, WAVE_REVERB = range(4)                 # srhip_wave_effect ops (srhip.h: SR_WAVE_*)
+WAVE_STEP_ONE = 1 << 32                                                     # a resample step is 32.32 fixed point
+FREEVERB_DELAYS = (1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617, 556, 441, 341, 225)      # eight combs, four allpasses, in samples at 44.1 kHz
+
+
+def reverb_delays(sample_rate):
+    """The 12 delays of srhip_wave_effect's reverb at ``sample_rate``: max(1, round(d * sample_rate / 44100)), halves rounded up."""
+    import numpy as np
+    return np.maximum(1, np.floor(np.array(FREEVERB_DELAYS, dtype=np.float64) * float(sample_rate) / 44100.0 + 0.5)).astype(np.int32)
+
+
+def wave_effect_len(n, op, param):
+    """The length rule of srhip_wave_effect: m = max(1, (n << 32) // step) for a resample, m = n otherwise (numpy arrays, int64 arithmetic)."""
+    import numpy as np
+    n, op, param = np.asarray(n, dtype=np.int64), np.asarray(op), np.asarray(param, dtype=np.int64)
+    step = np.where(op == WAVE_RESAMPLE, param, WAVE_STEP_ONE)
+    return np.where(op == WAVE_RESAMPLE, np.maximum(1, (n << 32) // np.maximum(step, 1)), n)
+
+
+def check_wave_effect(src_row, op, param, dst_len, row_len, pitch):
+    """The host-side argument check of ``wave_effect``: what the kernel cannot decide -- the rows against the store (as check_wave_rows), the
+    ops and resample steps, and ``dst_len`` against the op's length rule and the pitch."""
+    import numpy as np
+    src_row, op, param, dst_len, row_len = (np.asarray(a) for a in (src_row, op, param, dst_len, row_len))
+    if src_row.ndim != 1 or not (src_row.shape == op.shape == param.shape == dst_len.shape):
+        raise ValueError("wave_effect: src_row, op, param and dst_len must be 1-D arrays of one length, got %s %s %s %s"
+                         % (src_row.shape, op.shape, param.shape, dst_len.shape))
+    if src_row.size == 0:
+        return
+    if src_row.min() < 0 or src_row.max() >= len(row_len):
+        raise IndexError("wave_effect: src_row outside the store's %d rows" % len(row_len))
+    if op.min() < WAVE_COPY or op.max() > WAVE_REVERB:
+        raise ValueError("wave_effect: op outside 0..3 (copy, gain, resample, reverb)")
+    rs = op == WAVE_RESAMPLE
+    if rs.any() and (param[rs].min() < WAVE_STEP_ONE >> 1 or param[rs].max() > WAVE_STEP_ONE << 1):
+        raise ValueError("wave_effect: a resample step outside [2^31, 2^33] (a speed outside [0.5, 2])")
+    n = row_len[src_row].astype(np.int64)
+    if n.min() <= 0 or n.max() > 1 << 30:
+        raise ValueError("wave_effect: a source row of %d samples (1 .. 2^30 are supported)" % (n.min() if n.min() <= 0 else n.max()))
+    want = wave_effect_len(n, op, param)
+    if (dst_len != want).any():
+        b = int(np.flatnonzero(dst_len != want)[0])
+        raise ValueError("wave_effect: dst_len[%d] = %d, but op %d maps %d samples to %d" % (b, dst_len[b], op[b], n[b], want[b]))
+    if dst_len.max() > pitch:
+        raise ValueError("wave_effect: dst_len %d does not fit the destination's pitch %d" % (dst_len.max(), pitch))
+
+
+def wave_effect(store, row_off, row_len, src_row, op, param, dst_len, dst, delays, host):
+    """One effect slot of the device-made strong waveform view (srhip.h: srhip_wave_effect): row b of ``dst`` (fp32 [>= B, pitch], contiguous,
+    pitch % 4 == 0) becomes ``dst_len[b]`` samples of clip ``src_row[b]`` of the flat fp32 ``store`` after copy / gain / resample / reverb
+    (``op[b]``, ``param[b]``); the rest of the row is not written.  src_row int64, op int32, param int64, dst_len int32, all [B] on the device;
+    ``delays``: the 12 reverb delays (``reverb_delays``, host int32).  ``host``: (src_row, op, param, dst_len, row_len) as numpy arrays, the
+    values the device arrays were copied from: checked here (check_wave_effect) and handed to the entry, which checks them again."""
+    import numpy as np
+    if store.dtype != torch.float32 or row_off.dtype != torch.int64 or row_len.dtype != torch.int32:
+        raise ValueError("wave_effect: the store is fp32 with int64 row_off and int32 row_len, got %s / %s / %s" % (store.dtype, row_off.dtype, row_len.dtype))
+    if row_off.shape != row_len.shape or row_off.dim() != 1:
+        raise ValueError("wave_effect: row_off and row_len hold one entry per clip")
+    B = int(src_row.shape[0]) if src_row.dim() == 1 else -1
+    if (src_row.dtype, op.dtype, param.dtype, dst_len.dtype) != (torch.int64, torch.int32, torch.int64, torch.int32) \
+            or not (tuple(op.shape) == tuple(param.shape) == tuple(dst_len.shape) == (B,)):
+        raise ValueError("wave_effect: src_row int64, op int32, param int64 and dst_len int32 are [B] arrays, got %s %s / %s %s / %s %s / %s %s"
+                         % (src_row.dtype, tuple(src_row.shape), op.dtype, tuple(op.shape), param.dtype, tuple(param.shape), dst_len.dtype, tuple(dst_len.shape)))
+    if dst.dtype != torch.float32 or dst.dim() != 2 or not dst.is_contiguous() or dst.shape[0] < B or dst.shape[1] % 4:
+        raise ValueError("wave_effect: dst is a contiguous fp32 [>= B, pitch] buffer with pitch %% 4 == 0, got %s %s" % (dst.dtype, tuple(dst.shape)))
+    if store.untyped_storage().data_ptr() == dst.untyped_storage().data_ptr():
+        raise ValueError("wave_effect: source and destination are the same buffer (a row is read while others are written)")
+    h_src, h_op, h_param, h_len, h_row_len = host
+    h_op, h_param, h_len = (np.ascontiguousarray(a, dtype=t) for a, t in ((h_op, np.int32), (h_param, np.int64), (h_len, np.int32)))
+    if h_op.shape != (B,):
+        raise ValueError("wave_effect: the host arrays hold %s entries for %d device rows" % (h_op.shape, B))
+    check_wave_effect(h_src, h_op, h_param, h_len, h_row_len, int(dst.shape[1]))
+    delays = np.ascontiguousarray(delays, dtype=np.int32)
+    if delays.shape != (12,):
+        raise ValueError("wave_effect: delays holds the 12 reverb delays (reverb_delays(sample_rate)), got shape %s" % (delays.shape,))
+    _call("srhip_wave_effect", _p(store), _p(row_off), _p(row_len), int(row_len.shape[0]), _p(src_row), _p(op), _p(param), _p(dst_len), B, _p(dst),
+          int(dst.shape[1]), h_op.ctypes.data, h_param.ctypes.data, h_len.ctypes.data, delays.ctypes.data, _s())
+    return dst
+
+
 def check_token_rows(src_row, row_len):
     """The host-side argument check of ``token_view``: numpy ``src_row`` (where a loader produces it) against the numpy ``row_len`` of the
     store.  The kernel turns such a row into an all-pad row; here it is an error."""
