@@ -297,7 +297,7 @@ int srhip_patch_assemble(const float* tok, const float* bp, const float* cls, co
 int srhip_patch_grad_operands(const float* dx, void* dx_tok_bf16, float* dpos, float* dcls, int B, int Np, int D, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Split-bf16 ("bf16x3") forward of the rows that decide the pseudo-label masks (read_rows_precision = bf16x3; csrc/precise.hip).
+ * Split-bf16 ("bf16x3") forward of the rows that decide the pseudo-label masks (read_rows_precision = bf16x3; csrc/x3.hip).
  * Every fp32 operand x is split into hi = bf16_rne(x), lo = bf16_rne(x - hi); a product is hi.hi + hi.lo + lo.hi on the bf16 MFMA with fp32
  * accumulation (lo.lo dropped): ~4e-6 relative error against fp64 where the bf16 operands of srhip_gemm_nt give ~2e-3.  Activations are fp32.
  *
@@ -306,6 +306,7 @@ int srhip_patch_grad_operands(const float* dx, void* dx_tok_bf16, float* dpos, f
  *   SRHIP_X3_EPI_F32       : C = acc + bias
  *   SRHIP_X3_EPI_GELU_F32  : C = gelu_erf(acc + bias)                                               (nn.GELU(), vit.py:63,72)
  *   SRHIP_X3_EPI_RESID_F32 : C = C + row_scale[m / rows_per_sample] * (acc + bias), row_scale NULL = 1  (DropPath + residual, vit.py:164-165)
+ * The three are epilogues of the 128 x 128-tile engine that srhip_gemm_x3 and srhip_gemm_tn_x3_grouped launch too (gemm_x3_kernel, one main loop).
  * bias may be NULL.  Requirements: K % 32 == 0, lda >= K and ldw >= K multiples of 4, ldc >= N, A and W 16-byte aligned; any M (ragged tails
  * included) up to 65535 * 128 rows, any N.  row_scale only with SRHIP_X3_EPI_RESID_F32.
  * srhip_attn_fwd_x3: head_dim 64, qkv fp32 [B*N, 3*H*64] as srhip_gemm_nt_x3 writes it, out fp32 [B*N, H*64]; QK^T and PV as bf16x3 products,
@@ -325,11 +326,11 @@ int srhip_layernorm_fwd_f32(const float* x, const float* gamma, const float* bet
 int srhip_patch_im2col_f32(const float* img, const int* img_index, float* out, int B, int C, int HW, int ps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Split-bf16 ("bf16x3") kernels of the gradient rows (grad_rows_precision = bf16x3; csrc/precise_bwd.hip, same product scheme as above).
+ * Split-bf16 ("bf16x3") kernels of the gradient rows (grad_rows_precision = bf16x3; csrc/x3.hip, same product scheme and same kernels as above).
  *
- * srhip_attn_fwd_x3_lse: srhip_attn_fwd_x3 that also writes lse fp32 [B,H,N] = rowmax + log(rowsum) of the scaled scores (the backward's
+ * srhip_attn_fwd_x3_lse: srhip_attn_fwd_x3 (the same kernel template, the same out bits) that also writes lse fp32 [B,H,N] = rowmax + log(rowsum) of the scaled scores (the backward's
  *   statistic).  Same requirements.
- * srhip_gemm_x3: one 128 x 128-tile engine, fp32 operands, fp32 C.
+ * srhip_gemm_x3: the 128 x 128-tile engine of srhip_gemm_nt_x3 (NT GELU_PRE and NT GELU_F32 write the same C bits), fp32 operands, fp32 C.
  *   SRHIP_X3B_NT: C[M,N] = A[M,K] . B[N,K]^T; epilogue SRHIP_X3B_EPI_GELU_PRE only: v = acc + bias, aux_out[m*ldaux+n] = v, C = gelu_erf(v)
  *     (fc1 of a row that keeps its activations, vit.py:69-72).  lda, ldb >= K.
  *   SRHIP_X3B_NN: C[M,N] = epi(A[M,K] . B[K,N]) -- the input gradient dY . W with W read from the fp32 parameter block as it is stored.

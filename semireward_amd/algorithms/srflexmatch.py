@@ -378,7 +378,7 @@ def read_rows_precision(args, net_cls=None):
     """Numeric mode of the rows that decide masks, pseudo labels and rewards (the weak rows of every pass): ``args.read_rows_precision``, else
     the environment variable SR_READ_ROWS_PRECISION, else "bf16".
       bf16   : bf16 GEMM operands, fp32 accumulation -- the engine's one mode, bit for bit;
-      bf16x3 : split-bf16 products and fp32 activations (csrc/precise.hip), ~500x closer to the reference's fp32 forward.
+      bf16x3 : split-bf16 products and fp32 activations (csrc/x3.hip), ~500x closer to the reference's fp32 forward.
     Raises ValueError for another value, NotImplementedError for bf16x3 on a backbone without that forward (``precise_rows``)."""
     v = getattr(args, "read_rows_precision", None)
     if v is None:
@@ -399,7 +399,7 @@ def grad_rows_precision(args, net_cls=None):
     """Numeric mode of the rows that carry the backward (the labelled rows of pass 0, the strong rows of the last pass):
     ``args.grad_rows_precision``, else the environment variable SR_GRAD_ROWS_PRECISION, else "bf16".
       bf16   : bf16 GEMM / attention operands and saved activations, the bf16 hand-written backward -- bit for bit the engine's one mode;
-      bf16x3 : split-bf16 products and fp32 activations in the forward AND the backward of those rows (csrc/precise_bwd.hip).
+      bf16x3 : split-bf16 products and fp32 activations in the forward AND the backward of those rows (csrc/x3.hip).
     Independent of read_rows_precision; both set to bf16x3 give a step that follows the fp32 reference end to end.
     Raises ValueError for another value, NotImplementedError for bf16x3 on a backbone without that backward (``precise_grad_rows``)."""
     v = getattr(args, "grad_rows_precision", None)

@@ -418,7 +418,7 @@ class VisionTransformer(ModuleSurface):
 
     def _forward_x3(self, img, img_index, droppath, B, buftag, out, tree=None, save=False):
         """forward_features in split-bf16 precision (read_rows_precision / grad_rows_precision = bf16x3): every product is hi.hi + hi.lo +
-        lo.hi of the bf16 planes of its fp32 operands (csrc/precise.hip), activations stay fp32, LayerNorm / softmax / GELU / residual / head
+        lo.hi of the bf16 planes of its fp32 operands (csrc/x3.hip), activations stay fp32, LayerNorm / softmax / GELU / residual / head
         in fp32 in the order of vit.py.  The weights are read from the fp32 parameter block.  Own workspaces (tag "p"): the bf16 chain's
         buffers are not touched.  save: the same products and order, every activation kept fp32 in the persistent context of
         _ctx_buffers(B, "bf16x3") (LayerNorm statistics, the fc1 pre-activation, the attention lse) for backward(ctx.precision = "bf16x3")."""

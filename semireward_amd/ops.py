@@ -657,12 +657,12 @@ def patch_grad_operands(dx, dx_tok, dpos, dcls, B, Np, D):
     _call("srhip_patch_grad_operands", _p(dx), _p(dx_tok), _p(dpos), _p(dcls), B, Np, D, _s())
 
 
-# ---- split-bf16 (bf16x3) forward of the rows that decide the masks (csrc/precise.hip) ---------------------------------------------------
+# ---- split-bf16 (bf16x3) forward of the rows that decide the masks (csrc/x3.hip) --------------------------------------------------------
 def gemm_nt_x3(epi, A, W, C, M, N, K, *, lda=None, ldw=None, ldc=None, bias=None, row_scale=None, rows_per_sample=0):
     """C[M,N] = epilogue(A[M,K] . W[N,K]^T), fp32 operands as bf16 hi / lo planes, three MFMAs per fragment pair (see srhip_gemm_nt_x3)."""
     args = (epi, _p(A), lda or K, _p(W), ldw or K, _p(C), ldc or N, M, N, K, _p(bias), _p(row_scale), rows_per_sample, _s())
     if _PROFILE is not None:        # flops: the fp32-equivalent product (3x that on the MFMA); bytes: fp32 operands once + C (read too for RESID)
-        _PROFILE.timed("srhip_gemm_nt_x3", args, 2.0 * M * N * K, "gemm_nt_x3_kernel<%d>" % epi,
+        _PROFILE.timed("srhip_gemm_nt_x3", args, 2.0 * M * N * K, "gemm_x3_kernel<nt, %s>" % ("f32", "gelu", "resid")[epi],
                        4.0 * (M * K + N * K) + 4.0 * M * N * (2 if epi == X3_EPI_RESID_F32 else 1))
         return
     _call("srhip_gemm_nt_x3", *args)
@@ -671,7 +671,7 @@ def gemm_nt_x3(epi, A, W, C, M, N, K, *, lda=None, ldw=None, ldc=None, bias=None
 def attn_fwd_x3(qkv, out, B, N, H, scale):
     """out fp32 [B*N, H*64] = softmax(Q K^T * scale) V from qkv fp32 [B*N, 3*H*64], both products bf16x3 (srhip_attn_fwd_x3)."""
     if _PROFILE is not None:        # flops: QK^T (taken twice: max pass + exp pass) + PV as fp32-equivalent work; bytes: qkv in, out
-        _PROFILE.timed("srhip_attn_fwd_x3", (_p(qkv), _p(out), B, N, H, scale, _s()), 4.0 * B * H * N * N * 64, "attn_fwd_x3_kernel",
+        _PROFILE.timed("srhip_attn_fwd_x3", (_p(qkv), _p(out), B, N, H, scale, _s()), 4.0 * B * H * N * N * 64, "attn_fwd_x3_kernel<false>",
                        4.0 * B * N * 4 * H * 64)
         return
     _call("srhip_attn_fwd_x3", _p(qkv), _p(out), B, N, H, scale, _s())
@@ -685,12 +685,12 @@ def patch_im2col_f32(img, img_index, out, B, C, HW, ps):
     _call("srhip_patch_im2col_f32", _p(img), _p(img_index), _p(out), B, C, HW, ps, _s())
 
 
-# ---- split-bf16 (bf16x3) gradient rows (csrc/precise_bwd.hip) ---------------------------------------------------------------------------
+# ---- split-bf16 (bf16x3) gradient rows (csrc/x3.hip, the same tile engine) ------------------------------------------------------------
 def attn_fwd_x3_lse(qkv, out, lse, B, N, H, scale):
     """attn_fwd_x3 that also writes lse fp32 [B, H, N] for attn_bwd_x3 (srhip_attn_fwd_x3_lse)."""
     args = (_p(qkv), _p(out), _p(lse), B, N, H, scale, _s())
     if _PROFILE is not None:
-        _PROFILE.timed("srhip_attn_fwd_x3_lse", args, 4.0 * B * H * N * N * 64, "attn_fwd_x3_lse_kernel", 4.0 * B * N * 4 * H * 64)
+        _PROFILE.timed("srhip_attn_fwd_x3_lse", args, 4.0 * B * H * N * N * 64, "attn_fwd_x3_kernel<true>", 4.0 * B * N * 4 * H * 64)
         return
     _call("srhip_attn_fwd_x3_lse", *args)
 
@@ -702,7 +702,7 @@ def gemm_x3(layout, epi, A, B, C, M, N, K, *, lda=None, ldb=None, ldc=None, bias
     args = (layout, epi, _p(A), lda or K, _p(B), ldb, _p(C), ldc or N, M, N, K, _p(bias), _p(aux), _p(aux_out), ldaux, _s())
     if _PROFILE is not None:        # flops: the fp32-equivalent product; bytes: fp32 operands once + C (+ aux / C read)
         extra = 1 if (epi == X3B_EPI_ACC or aux is not None or aux_out is not None) else 0
-        _PROFILE.timed("srhip_gemm_x3", args, 2.0 * M * N * K, "gemm_x3_kernel<%s, %d>" % ("nt" if layout == X3B_NT else "nn", epi),
+        _PROFILE.timed("srhip_gemm_x3", args, 2.0 * M * N * K, "gemm_x3_kernel<%s, %s>" % ("nt" if layout == X3B_NT else "nn", ("f32", "acc", "dgelu", "gelu_pre")[epi]),
                        4.0 * (M * K + N * K) + 4.0 * M * N * (1 + extra))
         return
     _call("srhip_gemm_x3", *args)

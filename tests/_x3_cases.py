@@ -1,5 +1,5 @@
-"""The cases of tests/test_{cpu,gpu}_x3_cases.py: every split-bf16 ("bf16x3") kernel of csrc/precise.hip, csrc/precise_bwd.hip and csrc/x3.h
-(gemm_nt_x3_kernel with its three epilogues, gemm_x3_kernel NT GELU_PRE and NN F32 / ACC / DGELU, the grouped TN weight-gradient kernel with its
+"""The cases of tests/test_{cpu,gpu}_x3_cases.py: every split-bf16 ("bf16x3") kernel of csrc/x3.hip
+(gemm_x3_kernel NT with the three epilogues of srhip_gemm_nt_x3, NT GELU_PRE and NN F32 / ACC / DGELU of srhip_gemm_x3, the grouped TN weight-gradient kernel with its
 dbias column sums, attn_fwd_x3 with and without lse, both roles of attn_bwd_x3) and the fp32-output LayerNorm the x3 chain runs twice per block,
 element by element against float64.  Nothing is stored: every input is rebuilt from its seed, every expected value is recomputed.  Importing
 this module launches nothing and does not touch CUDA.
@@ -289,7 +289,7 @@ GEMM_CASES = tuple(
     + [_g("nn", e, *s, bias=False) for s in NN_SHAPES for e in ("f32", "acc", "dgelu")])
 GEMM_BY_ID = {c["id"]: c for c in GEMM_CASES}
 assert len(GEMM_BY_ID) == len(GEMM_CASES)
-KERNEL = {"nt3": "gemm_nt_x3_kernel", "nt": "gemm_x3_kernel<NT>", "nn": "gemm_x3_kernel<NN>"}
+KERNEL = {"nt3": "gemm_x3_kernel<NT>", "nt": "gemm_x3_kernel<NT>", "nn": "gemm_x3_kernel<NN>"}
 
 
 @functools.lru_cache(maxsize=4)
@@ -822,7 +822,7 @@ def _sum32(x, reverse):
 
 
 def restate_fwd(q, k, v, mode="x3", reverse=False, fault=None):
-    """one head of attn_fwd_x3_wave in float32: out [N, 64], lse [N] (float64 arrays of the float32 values)"""
+    """one head of attn_fwd_x3_kernel in float32: out [N, 64], lse [N] (float64 arrays of the float32 values)"""
     N = q.shape[0]
     q, k, v = q.astype(F), k.astype(F), v.astype(F)
     s = x3_acc(*planes(k, mode), *planes(q, mode), reverse).T

@@ -84,7 +84,7 @@ def test_invalid_arguments_return_error_codes_without_gpu():
         assert lib.srhip_w2v_pos_finish_bwd(a, a, a, a, a, a, a, a, a, a, 2, 10, 16, 16, D, 0, 0, 1.0, None) == E
     assert lib.srhip_w2v_spec_mask_bwd(a, None, None, None, 2, 10, 16, 16, 96, None) == E                 # D % 64 != 0
     assert lib.srhip_w2v_spec_mask_bwd(a, None, a, None, 2, 10, 16, 16, 128, None) == E                   # mask without dembed
-    # ViT glue and backward (vit_ops.hip, precise_bwd.hip, pass_tree.hip), same pattern
+    # ViT glue and backward (vit_ops.hip, x3.hip, pass_tree.hip), same pattern
     for fn in (lib.srhip_layernorm_bwd_part, lib.srhip_layernorm_bwd_part_f32):
         assert fn(a, a, a, a, a, a, a, 0, a, None, 0, 4112, 384, None) == E                               # n_rep = 0
         assert fn(a, a, a, a, a, a, None, 16, a, None, 0, 4112, 384, None) == E                           # no partial copies

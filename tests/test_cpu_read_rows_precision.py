@@ -1,4 +1,4 @@
-"""read_rows_precision (bf16 | bf16x3) without a GPU: the C ABI and its wrappers, the register budget of csrc/precise.hip, the option's
+"""read_rows_precision (bf16 | bf16x3) without a GPU: the C ABI and its wrappers, the register budget of csrc/x3.hip, the option's
 validation, the launch plan of the mode, and a CPU model of its numerics against the reference's golden vectors."""
 import argparse
 import os
@@ -30,13 +30,16 @@ def test_header_declares_the_x3_entries_and_ops_wraps_them():
 
 
 def test_precise_kernels_keep_their_register_budget(tmp_path):
-    """Compiled with the resource remarks on (as test_hot_kernels_keep_their_register_budget does): no scratch, no spill, two waves per SIMD."""
+    """Compiled with the resource remarks on (as test_hot_kernels_keep_their_register_budget does): every kernel of csrc/x3.hip -- the seven
+    instantiations of the one GEMM engine, the grouped TN kernel, both attention forwards, both attention backward kernels -- has no scratch,
+    no spill and two waves per SIMD."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
     csrc = os.path.join(ROOT, "semireward_amd", "csrc")
+    assert sorted(f for f in os.listdir(csrc) if "x3" in f or "precise" in f) == ["x3.hip"]
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-c",
-                        "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "o.o"), os.path.join(csrc, "precise.hip")],
+                        "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "o.o"), os.path.join(csrc, "x3.hip")],
                        capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     out, cur = {}, None
@@ -47,10 +50,20 @@ def test_precise_kernels_keep_their_register_budget(tmp_path):
         m = re.search(r"remark:\s+([A-Za-z \[\]/]+): (\d+)", line)
         if m and cur is not None:
             cur[m.group(1).strip()] = int(m.group(2))
-    gemm = {k: v for k, v in out.items() if "gemm_nt_x3_kernel" in k}
-    attn = {k: v for k, v in out.items() if "attn_fwd_x3_kernel" in k}
-    assert len(gemm) == 3 and len(attn) == 1, sorted(out)
-    for k, v in list(gemm.items()) + list(attn.items()):
+    # gemm_x3_kernel<LA, LB, EPI> as the Itanium ABI spells its arguments: layouts ROWS = 0 / COLS = 1, the file's epilogue enum in its order
+    epi = {n: i for i, n in enumerate(("F32", "ACC", "DGELU", "GELU_PRE", "GELU", "RESID"))}
+    want = {"gemm_x3_kernelILi0ELi%dELi%dEE" % (lb, epi[e]) for lb, es in ((0, ("F32", "GELU", "RESID", "GELU_PRE")), (1, ("F32", "ACC", "DGELU")))
+            for e in es}
+    gemm = {k: v for k, v in out.items() if "gemm_x3_kernel" in k}
+    assert len(gemm) == 7 and all(any(w in k for k in gemm) for w in want), sorted(out)
+    assert not any("gemm_nt_x3" in k for k in out), sorted(out)
+    rest = {}
+    for name, n in (("gemm_tn_x3_grouped_kernel", 1), ("attn_fwd_x3_kernelILb", 2), ("attn_bwd_x3_dq_kernel", 1), ("attn_bwd_x3_dkv_kernel", 1)):
+        hit = {k: v for k, v in out.items() if name in k}
+        assert len(hit) == n, (name, sorted(out))
+        rest.update(hit)
+    assert len(out) == len(gemm) + len(rest) + 1 and any("scale_rows_f32_kernel" in k for k in out), sorted(out)
+    for k, v in list(gemm.items()) + list(rest.items()):
         assert v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["Occupancy [waves/SIMD]"] >= 2, (k, v)
 
 

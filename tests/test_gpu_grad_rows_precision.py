@@ -1,4 +1,4 @@
-"""grad_rows_precision = bf16x3 on the GPU: the split-bf16 backward kernels (csrc/precise_bwd.hip) against fp64, the ViT backward of the
+"""grad_rows_precision = bf16x3 on the GPU: the split-bf16 backward kernels (csrc/x3.hip) against fp64, the ViT backward of the
 gradient rows against fp32 autograd, the reference step traces with both options on, and the captured step."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""read_rows_precision = bf16x3 on the GPU: the split-bf16 kernels (csrc/precise.hip) against fp64, the ViT forward of the read rows against
+"""read_rows_precision = bf16x3 on the GPU: the split-bf16 kernels (csrc/x3.hip) against fp64, the ViT forward of the read rows against
 the reference's golden vectors, the mask decisions of the reference sweep, which rows the mode touches, and the captured step."""
 import argparse
 import json

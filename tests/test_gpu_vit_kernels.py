@@ -1,4 +1,4 @@
-"""ViT glue and backward kernels (csrc/vit_ops.hip, precise_bwd.hip, pass_tree.hip), entry point by entry point, against float64 references
+"""ViT glue and backward kernels (csrc/vit_ops.hip, x3.hip, pass_tree.hip), entry point by entry point, against float64 references
 computed from exactly the bf16 / fp32 operands each kernel reads: the bounds below measure only the kernel's own arithmetic and output
 rounding.  Every comparison is over the full output tensor, element by element; outputs that accumulate start from nonzero values, and
 memory a kernel must not write holds a finite sentinel that is checked bit for bit.

@@ -1,11 +1,13 @@
-"""Every split-bf16 kernel of csrc/precise.hip, csrc/precise_bwd.hip and csrc/x3.h, and the fp32-output LayerNorm, per element against
+"""Every split-bf16 kernel of csrc/x3.hip, and the fp32-output LayerNorm, per element against
 float64, through the C ABI: the cases, arenas, references and bounds of tests/_x3_cases.py.  Every launch is made twice (the same bits), from
 operands whose padding is NaN into outputs whose padding must come back bit for bit.  Each test prints `headroom <id> <ratio>`, the largest
 |got - want| / bound, and asserts it is at most 1; the HEADROOM| lines feed tools/x3_cases_headroom.py."""
 import numpy as np
 import pytest
+import torch
 
 import _x3_cases as X
+from semireward_amd import ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -55,7 +57,7 @@ def test_attention_forward(cid):
     ratios = {"out": X.within(cid, "out", out, f["out"], f["out_tol"]), "lse": X.within(cid, "lse", lse, f["lse"], f["lse_tol"])}
     for a in outs:
         assert not a.pad_touched(), "%s: output padding overwritten" % cid
-    _report("attn_fwd_x3_kernel / attn_fwd_x3_lse_kernel", "fwd", cid, ratios)
+    _report("attn_fwd_x3_kernel<false> / attn_fwd_x3_kernel<true>", "fwd", cid, ratios)
 
 
 @pytest.mark.parametrize("cid", [c["id"] for c in X.ATTN_CASES])
@@ -70,3 +72,29 @@ def test_attention_backward(cid):
     for a in outs:
         assert not a.pad_touched(), "%s: output padding overwritten" % cid
     _report("attn_bwd_x3_dq_kernel + attn_bwd_x3_dkv_kernel", "bwd", cid, ratios)
+
+
+def _view_bits(arena):
+    return arena.view.cpu().contiguous().view(torch.int32).numpy().copy()
+
+
+@pytest.mark.parametrize("M,N,K", [(1, 1, 32), (129, 132, 96), (300, 127, 64)])
+def test_both_gemm_entry_points_are_one_engine(M, N, K):
+    """srhip_gemm_nt_x3 and srhip_gemm_x3 launch the same tile engine (csrc/x3.hip): on the same operands, with bias, ldc = N + 3 and
+    ldaux = N + 4, the pre-activation GELU_PRE keeps has the bits of the F32 launch's C, and its C has the bits of the GELU_F32 launch's C.
+    One tile with one row, a ragged 2 x 2 tile grid with three k-steps, a ragged N."""
+    L = X.GemmLaunch(X._g("nt", "gelu_pre", M, N, K, ldc_pad=3), DEV)
+    assert L.ldc == N + 3 and L.ldaux == N + 4 and L.Bias is not None
+    got = {}
+    for name, epi in (("f32", ops.X3_EPI_F32), ("gelu", ops.X3_EPI_GELU_F32)):
+        ops.gemm_nt_x3(epi, L.A.ptr, L.B.ptr, L.C.ptr, M, N, K, lda=L.lda, ldw=L.ldb, ldc=L.ldc, bias=L.Bias.ptr)
+        torch.cuda.synchronize()
+        assert not L.C.pad_touched(), "%s: output padding overwritten" % name
+        got[name] = _view_bits(L.C)
+        L.C.reset()
+    L.run_hip()                                            # srhip_gemm_x3(NT, GELU_PRE)
+    for a in L.outs:
+        assert not a.pad_touched(), "gelu_pre: output padding overwritten"
+    assert np.isfinite(L.AuxOut.get()).all() and np.isfinite(L.C.get()).all()
+    assert np.array_equal(_view_bits(L.AuxOut), got["f32"]), "aux_out of GELU_PRE and C of srhip_gemm_nt_x3(F32) differ"
+    assert np.array_equal(_view_bits(L.C), got["gelu"]), "C of GELU_PRE and C of srhip_gemm_nt_x3(GELU_F32) differ"
