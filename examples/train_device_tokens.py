@@ -7,12 +7,16 @@ of a batch -- gather, right-padding to the batch's longest row, the lengths -- i
 
 SRSoftMatch takes a strong view: the unlabelled set carries two variants of every sentence (``data_s``), here a stand-in for the reference's
 back-translations (tokens dropped and swapped).  With strings instead of token arrays the sentences are tokenised once, at construction, by the
-tokenizer of the net's snapshot directory (``pretrain_path`` or the hub cache; configs/README.md).
+tokenizer of the net's snapshot directory (``pretrain_path`` or the hub cache; configs/README.md).  With ``--device-strong``
+(``device_tokens_strong: True``) there is no ``data_s``: the loader makes every strong view on the device from the clean sentence -- two
+token-level slots (delete / mask / cutoff / swap) drawn per sample and epoch, one launch (csrc/token_strong.hip) -- and a strong-view algorithm
+trains on sentences that have no back-translations.
 
     python examples/train_device_tokens.py --steps 60
     python examples/train_device_tokens.py --steps 60 --algorithm srpseudolabel
     python examples/train_device_tokens.py --steps 60 --run-hooks     # the reference's evaluation / checkpoint / logging hooks drive the run
     python examples/train_device_tokens.py --steps 20 --net base      # BERT-base (random init unless a snapshot is on disk), max_length 128
+    python examples/train_device_tokens.py --steps 60 --device-strong # SRFlexMatch, strong views made on the device, no data_s
 """
 import argparse
 import os
@@ -26,10 +30,10 @@ from semireward_amd.algorithms import get_algorithm          # noqa: E402
 from semireward_amd.core.hooks import Hook                   # noqa: E402
 from semireward_amd.nets import bert                         # noqa: E402
 
-CLS, SEP, FIRST = 2, 3, 5                                     # [CLS], [SEP], the first ordinary id of the synthetic vocabulary
+CLS, SEP, FIRST = 2, 3, 5                                     # [CLS], [SEP], the first ordinary id of the synthetic vocabulary (4: its [MASK])
 # the engine keeps one set of workspace buffers per distinct (B, L): the lengths stay a handful of values (configs/README.md)
-NETS = {"tiny": dict(builder=bert.bert_tiny_test, vocab=120, lengths=(8, 16, 24, 32), feature_dim=128, lr=5e-4),
-        "base": dict(builder=bert.bert_base_uncased, vocab=30522, lengths=(32, 64, 96, 128), feature_dim=768, lr=5e-5)}
+NETS = {"tiny": dict(builder=bert.bert_tiny_test, vocab=120, lengths=(8, 16, 24, 32), feature_dim=128, lr=5e-4, mask_id=4),
+        "base": dict(builder=bert.bert_base_uncased, vocab=30522, lengths=(32, 64, 96, 128), feature_dim=768, lr=5e-5, mask_id=103)}
 
 
 def synth_rows(n, num_classes, vocab, lengths, seed):
@@ -66,7 +70,8 @@ class PrintHook(Hook):
 
 
 ALGORITHMS = {"srpseudolabel": dict(unsup_warm_up=0.4, p_cutoff=0.95),
-              "srsoftmatch": dict(dist_align=True, dist_uniform=True, per_class=False, ema_p=0.999, n_sigma=2)}
+              "srsoftmatch": dict(dist_align=True, dist_uniform=True, per_class=False, ema_p=0.999, n_sigma=2),
+              "srflexmatch": dict(thresh_warmup=True, p_cutoff=0.95)}
 
 
 def main():
@@ -76,16 +81,19 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--net", choices=sorted(NETS), default="tiny")
-    ap.add_argument("--algorithm", choices=sorted(ALGORITHMS), default="srsoftmatch")
+    ap.add_argument("--algorithm", choices=sorted(ALGORITHMS), default=None, help="srsoftmatch; srflexmatch with --device-strong")
+    ap.add_argument("--device-strong", action="store_true",
+                    help="device_tokens_strong: the strong views are made on the device from the clean sentences, no data_s")
     ap.add_argument("--run-hooks", action="store_true",
                     help="run_hooks + device_eval: evaluate and checkpoint every steps / 2 steps (into a temporary save_dir), log every 10")
     a = ap.parse_args()
+    a.algorithm = a.algorithm or ("srflexmatch" if a.device_strong else "srsoftmatch")
     C, net = a.classes, NETS[a.net]
     x_lb, y_lb = synth_rows(10 * C, C, net["vocab"], net["lengths"], 1)
     x_ulb, _ = synth_rows(512, C, net["vocab"], net["lengths"], 2)
     x_te, y_te = synth_rows(128, C, net["vocab"], net["lengths"], 3)
     ulb = {"data": x_ulb, "targets": None}
-    if a.algorithm == "srsoftmatch":                          # its train_step takes x_ulb_s: two variants per sentence
+    if a.algorithm != "srpseudolabel" and not a.device_strong:   # its train_step takes x_ulb_s: two variants per sentence
         rng = np.random.Generator(np.random.PCG64(4))
         ulb["data_s"] = [[variant(r, rng) for r in x_ulb] for _ in range(2)]
     steps = max(a.steps, a.epochs) // a.epochs * a.epochs
@@ -95,7 +103,7 @@ def main():
         feature_dim=net["feature_dim"], sr_lr=5e-4, sr_ema=False, sr_ema_m=0.99, gpu=0, rank=0, world_size=1, distributed=False, seed=0,
         # the input pipeline: what a usb_nlp yaml says (max_length, batch sizes, sampler) + the rows + the option
         dataset="synthetic_tokens", max_length=max(net["lengths"]), batch_size=a.batch, uratio=1, eval_batch_size=16,
-        train_sampler="RandomSampler", device_tokens=True,
+        train_sampler="RandomSampler", device_tokens=True, device_tokens_strong=a.device_strong, device_tokens_mask_id=net["mask_id"],
         dataset_dict={"train_lb": {"data": x_lb, "targets": y_lb}, "train_ulb": ulb, "eval": {"data": x_te, "targets": y_te}},
         **ALGORITHMS[a.algorithm])
     if a.run_hooks:

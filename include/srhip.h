@@ -879,6 +879,31 @@ int srhip_wave_effect(const float* store, const long long* row_off, const int* r
 int srhip_token_view(const int* store, const long long* row_off, const int* row_len, int n_rows, const long long* src_row, int B, int L,
                      int pad_id, long long* ids, int ld_ids, int* key_len, void* stream);
 
+/* ---- the strong view of a token batch made on the device from the CLEAN sentence (``device_tokens_strong: True``,
+ * semireward_amd/data/device_tokens.py): a srhip_token_view row after two token-level slots, one launch.  The chain is the engine's own -- not
+ * the reference's back-translation --; tests/_token_strong_cases.py restates it in integers (strong_row_ref).
+ *   store / row_off / row_len / src_row / ids / ld_ids / key_len   as srhip_token_view
+ *   slot0, slot1   int64 [B]: bits 0..7 op, bits 8..31 the count c, bits 32..63 seed;  Lsrc the longest source row taken (1 .. 4096: the
+ *                  row and its keys share LDS, 32 KiB at the cap);  mask_id what SR_TOKEN_MASK writes
+ * A row is t[0 .. n - 1], n = min(row_len[r], Lsrc); t[0] ([CLS]) and t[n - 1] ([SEP]) are never moved, changed or removed; the interior is
+ * positions 1 .. n - 2, ni = max(0, n - 2) of them.  Slot 0, then slot 1 on the row and the ni that slot 0 left; c is clamped to 0 .. ni:
+ *   SR_TOKEN_COPY    nothing (an op above 4 acts the same)
+ *   SR_TOKEN_DELETE  interior position i is removed iff rank_i < c, with key_i = fmix32(seed + i * 0x9E3779B1) (csrc/common.h, mod 2^32) and
+ *                    rank_i = the number of interior j with key_j < key_i (the keys of a row are pairwise distinct); n -= c
+ *   SR_TOKEN_MASK    the same selection; the selected tokens become mask_id
+ *   SR_TOKEN_CUTOFF  the c positions from start = 1 + fmix32(seed) % (ni - c + 1) on are removed; n -= c
+ *   SR_TOKEN_SWAP    for k = 0 .. c - 1 in order: a = 1 + fmix32(seed + 2k * 0x9E3779B1) % ni, b = 1 + fmix32(seed + (2k + 1) * 0x9E3779B1) % ni,
+ *                    t[a] <-> t[b]; nothing when ni < 2
+ * Then ids[b, t] = t[t] for t < m = min(n, L), pad_id for m <= t < L, key_len[b] = m; columns L .. ld_ids are not written.  A src_row outside
+ * [0, n_rows) gives an all-pad row of length 0.  Nothing past a stored row is read.  One workgroup per row, no atomics: equal inputs give
+ * equal bits.  SR_EINVAL: a null pointer, n_rows <= 0, B outside 1 .. 65535, Lsrc outside 1 .. 4096, L <= 0, ld_ids < L, store not 16-byte
+ * aligned, ids not 8-byte aligned, a negative pad_id or mask_id. */
+enum { SR_TOKEN_COPY = 0, SR_TOKEN_DELETE = 1, SR_TOKEN_MASK = 2, SR_TOKEN_CUTOFF = 3, SR_TOKEN_SWAP = 4 };
+enum { SR_TOKEN_STRONG_MAX_LSRC = 4096 };
+int srhip_token_strong(const int* store, const long long* row_off, const int* row_len, int n_rows, const long long* src_row,
+                       const long long* slot0, const long long* slot1, int B, int Lsrc, int L, int pad_id, int mask_id, long long* ids,
+                       int ld_ids, int* key_len, void* stream);
+
 /* ---- WideResNet building blocks (classic_cv backbone, semilearn/nets/wrn/wrn.py; BASELINE.json configs[0], parity configuration) ----
  * Feature maps are NHWC = row-major [rows = B*H*W, C].  conv = im2col (bf16) + srhip_gemm_nt; dW = srhip_gemm_tn_grouped_f32(dY, col);
  * dX = srhip_gemm_nt(dY, W^T) + col2im.

@@ -179,6 +179,7 @@ SIGNATURES = {
     "srhip_wave_view": (I, [P, P, P, I, P, P, I, I, I, P, I, P]),
     "srhip_wave_effect": (I, [P, P, P, I, P, P, P, P, I, P, I, P, P, P, P, P]),
     "srhip_token_view": (I, [P, P, P, I, P, I, I, I, P, I, P, P]),
+    "srhip_token_strong": (I, [P, P, P, I, P, P, P, I, I, I, I, I, P, I, P, P]),
     "srhip_gemm_nt_dropout": (I, [I, P, I, P, I, P, I, I, I, I, P, P, P, I, U, U, F, P]),
     "srhip_w2v_conv0": (I, [I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P]),
     "srhip_w2v_conv_weight_prep": (I, [P, P, P, I, I, I, P]),

@@ -114,6 +114,9 @@ class AlgorithmBase:
         if g("device_audio_strong", False) and not self.device_audio:       # the strong waveform view made on the device needs the resident clips
             from ..data.device_audio import device_strong
             device_strong(args)                              # (raises)
+        if g("device_tokens_strong", False) and not self.device_tokens:     # the strong token view made on the device needs the resident sentences
+            from ..data.device_tokens import device_strong
+            device_strong(args)                              # (raises)
         self.input_mode = None                               # the record of the one device input mode that is on (data/modes.py)
         if self.device_data or self.device_audio or self.device_tokens:      # no key: nothing under data/ is imported
             from ..data.modes import active_mode

@@ -11,7 +11,11 @@ Restates
   semilearn/datasets/samplers/sampler.py:55-73             the epoch's index stream (EpochSampler of data/device_loader.py, unchanged)
 One deviation, documented in configs/README.md: the reference picks the strong variant with an unseeded ``random.randint(1, 2)`` in every
 worker process; here the pick comes from a numpy generator seeded with (seed, rank, loader role, epoch), so the draws cannot be matched.  The
-sampler stream, the tokenisation and the padding are matched exactly (tests/golden/device_tokens.npz)."""
+sampler stream, the tokenisation and the padding are matched exactly (tests/golden/device_tokens.npz).
+
+``device_tokens_strong: True`` makes the strong view on the device from the clean sentence instead of reading a stored variant: two
+token-level slots (delete / mask / cutoff / swap) drawn per sample and epoch, one srhip_token_strong launch (csrc/token_strong.hip).  That
+chain is the engine's own, not the reference's back-translation; tests/_token_strong_cases.py restates it exactly."""
 import os
 
 import numpy as np
@@ -106,6 +110,30 @@ def _view(ds, src_row, L):
     return TokenBatch(*ops.token_view(ds.store, ds.row_off, ds.row_len, src_row, L, ds.pad_id))
 
 
+STRONG_KEY = "device_tokens_strong"
+STRONG_RATE_KEY, MASK_ID_KEY = "device_tokens_strong_rate", "device_tokens_mask_id"
+STRONG_RATE = 0.3                 # a design default, not a measurement: the upper end of the 0.1 .. 0.3 token-level augmentation papers use
+MASK_ID = 103                     # [MASK] of both reference vocabularies (bert-base-uncased / bert-base-cased)
+
+
+def draw_token_slots(rng, n0, rate):
+    """The strong view's draws for rows of ``n0`` tokens from ``rng``, whole-epoch vectors in this order: op [2, N] = rng.integers(1, 5)
+    (delete, mask, cutoff, swap; uniform, with replacement), u [2, N] = rng.random(), seed [2, N] = rng.integers(0, 2^32).  The counts are
+    c = floor(u * rate * ni) slot by slot, with the interior ni = max(0, n - 2) that slot meets (0 for a swap when ni < 2); 'len' int64 [3, N]
+    is the row, after slot 0, after slot 1 (ops.token_strong_len)."""
+    n0 = np.asarray(n0, dtype=np.int64)
+    op = rng.integers(1, 5, size=(2, n0.size))
+    u = rng.random((2, n0.size))
+    seed = rng.integers(0, 2 ** 32, size=(2, n0.size))
+    c, lens = np.zeros_like(op), [n0]
+    for s in (0, 1):
+        ni = np.maximum(lens[s] - 2, 0)
+        c[s] = np.minimum(np.floor(u[s] * rate * ni).astype(np.int64), ni)
+        c[s][(op[s] == ops.TOKEN_SWAP) & (ni < 2)] = 0
+        lens.append(ops.token_strong_len(lens[s], op[s], c[s]))
+    return {"op": op, "c": c, "seed": seed, "len": np.stack(lens)}
+
+
 class TokenTrainLoader(RaggedTrainLoader):
     """Per-step dicts of one epoch: consecutive ``batch_size`` chunks of the sampler's stream (drop_last).  'idx_*' the dataset indices,
     'y_*' the targets, 'x_*' the sentence and 'x_*_s' one of its variants, picked uniformly -- every view a ``TokenBatch`` right-padded to
@@ -114,21 +142,56 @@ class TokenTrainLoader(RaggedTrainLoader):
     (``seed``, epoch): ``set_epoch`` / iterating again replays them.  Everything an epoch needs -- its index stream, targets and store rows --
     goes to the device in ONE copy when the epoch starts; the per-batch lengths are computed on the host from ``row_len_host`` (vectorised;
     nothing is read back from the device).  ``draws`` keeps the host arrays of the last epoch started:
-    {view key: (store rows int64 [N], padded length of every batch int64 [len(self)])}."""
+    {view key: (store rows int64 [N], padded length of every batch int64 [len(self)])}.
+
+    ``device_strong=True`` (``device_tokens_strong``): 'x_*_s' is made on the device from the CLEAN sentence instead -- two token-level slots
+    (delete / mask / cutoff / swap at ``rate``) drawn per sample and epoch (``draw_token_slots``), one srhip_token_strong launch, no host
+    synchronisation, no allocation besides the view.  The two packed slot rows ride behind the view's store rows in the same one copy and are
+    drawn last, so every other view is what it is without the option; the padded length of a batch is its longest OUTPUT row, by the host's
+    length rule.  ``strong_draws`` keeps the draws of the last epoch started: 'op' / 'c' / 'seed' int64 [2, N], 'len' int64 [3, N]."""
     mode_key, data_s_help = "device_tokens", DATA_S_HELP
+
+    def __init__(self, dataset, batch_size, sampler, strong=True, keys=("idx_lb", "x_lb", "y_lb"), seed=(0,), device_strong=False,
+                 rate=STRONG_RATE, mask_id=MASK_ID):
+        self.makes_strong = bool(device_strong)
+        super().__init__(dataset, batch_size, sampler, strong, keys, seed)
+        if self.makes_strong and any(self._is_strong(k) for k in self.keys):
+            if dataset.n_variants:
+                raise ValueError("%s: the unlabelled set carries data_s (pre-augmented variants) and the strong view is to be made on the device: "
+                                 "there must be one source of strong views -- drop data_s or the key" % STRONG_KEY)
+            self.rate, self.mask_id = check_strong_rate(rate), int(mask_id)
+            if self.mask_id < 0:
+                raise ValueError("%s: %s = %d is no token id" % (STRONG_KEY, MASK_ID_KEY, self.mask_id))
+            self.Lsrc = int(dataset.row_len_host.max())
+            if self.Lsrc > ops.TOKEN_STRONG_MAX_LSRC:
+                raise ValueError("%s: sentence %d holds %d tokens, more than the %d srhip_token_strong keeps in LDS"
+                                 % (STRONG_KEY, int(dataset.row_len_host.argmax()), self.Lsrc, ops.TOKEN_STRONG_MAX_LSRC))
+            self.strong_draws = None
 
     def _copy(self, table):
         return _h2d(table, self.dataset.device)
 
     def _draw(self, rng, key, src):
-        """No table row beyond the store rows; the padded length of every batch comes from the host's copy of the row lengths."""
+        """No table row beyond the store rows; the padded length of every batch comes from the host's copy of the row lengths.  A device-made
+        strong view adds its two packed slot rows, and its batches are as long as their longest output row."""
         lens, B, nb = self.dataset.row_len_host, self.batch_size, len(self)
         ops.check_token_rows(src, lens)
-        return [], (src, lens[src[:nb * B]].reshape(nb, B).max(axis=1).astype(np.int64))
+        if not (self.makes_strong and self._is_strong(key)):
+            return [], (src, lens[src[:nb * B]].reshape(nb, B).max(axis=1).astype(np.int64))
+        sd = self.strong_draws = draw_token_slots(rng, lens[src], self.rate)
+        slots = np.stack([ops.pack_token_slot(sd["op"][s], sd["c"][s], sd["seed"][s]) for s in (0, 1)])
+        padded = sd["len"][2][:nb * B].reshape(nb, B).max(axis=1).astype(np.int64)
+        ops.check_token_strong(src[:nb * B], slots[:, :nb * B], np.repeat(padded, B), lens, self.Lsrc)
+        return [slots[0], slots[1]], (src, padded)
 
     def _view_fn(self, dev, row, draw, key):
         ds, B, src, lengths = self.dataset, self.batch_size, dev[row], draw[1].tolist()
-        return lambda s, t: _view(ds, src[s:s + B], lengths[t])
+        if not (self.makes_strong and self._is_strong(key)):
+            return lambda s, t: _view(ds, src[s:s + B], lengths[t])
+        from ..nets.bert import TokenBatch
+        slot0, slot1, Lsrc, mask_id, token_strong = dev[row + 1], dev[row + 2], self.Lsrc, self.mask_id, ops.token_strong
+        return lambda s, t: TokenBatch(*token_strong(ds.store, ds.row_off, ds.row_len, src[s:s + B], slot0[s:s + B], slot1[s:s + B], lengths[t],
+                                                     Lsrc, ds.pad_id, mask_id))
 
 
 class TokenEvalLoader(RaggedEvalLoader):
@@ -188,6 +251,34 @@ def refuse_unsupported(args):
         raise NotImplementedError("device_tokens: train_sampler %r is not supported (only 'RandomSampler', the reference's DistributedSampler "
                                   "index stream, is restated on the device path)" % (sampler,))
     view_length(args)
+    device_strong(args)
+
+
+def device_strong(args):
+    """Whether ``device_tokens_strong`` is on -- refused without ``device_tokens``, whose resident token store it reads, and with a rate
+    outside (0, 1]."""
+    on = bool(getattr(args, STRONG_KEY, False))
+    if on and not getattr(args, "device_tokens", False):
+        raise ValueError("%s: True makes the strong token view on the device from the resident token store: it needs device_tokens: True" % STRONG_KEY)
+    if on:
+        check_strong_rate(getattr(args, STRONG_RATE_KEY, None))
+    return on
+
+
+def check_strong_rate(rate):
+    rate = STRONG_RATE if rate is None else rate
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 < float(rate) <= 1.0:
+        raise ValueError("%s: %s = %r must lie in (0, 1] (the largest share of a sentence's interior one slot touches)" % (STRONG_KEY, STRONG_RATE_KEY, rate))
+    return float(rate)
+
+
+def strong_mask_id(args, tokenizer=None):
+    """``device_tokens_mask_id`` when set; else the resolved tokenizer's ``mask_token_id``; else 103, [MASK] of both reference vocabularies."""
+    key = getattr(args, MASK_ID_KEY, None)
+    if key is not None:
+        return int(key)
+    tok = getattr(tokenizer, "mask_token_id", None)
+    return MASK_ID if tok is None else int(tok)
 
 
 def view_length(args):
@@ -206,6 +297,11 @@ def refuse_unsupported_model(model, dataset_dict=None):
     for name, ds in (dataset_dict or {}).items():
         if not isinstance(ds, DeviceTokenDataset):
             continue
+        mask_id = getattr(ds, "strong_mask_id", None)          # set where device_tokens_strong makes views of this set
+        if mask_id is not None and (mask_id >= model.cfg.vocab or mask_id == ds.pad_id or mask_id < 0):
+            raise ValueError("%s: %s = %d %s (set %s to the vocabulary's [MASK] id)"
+                             % (STRONG_KEY, MASK_ID_KEY, mask_id, "is the store's pad_id" if mask_id == ds.pad_id else
+                                "lies outside the model's vocabulary of %d" % model.cfg.vocab, MASK_ID_KEY))
         longest = int(ds.row_len_host.max()) if ds.max_length is None else ds.max_length
         if longest > model.cfg.max_pos:
             raise ValueError("device_tokens: max_length = %d of dataset %r exceeds the model's %d positions (max_pos)" % (longest, name, model.cfg.max_pos))
@@ -228,8 +324,12 @@ def build_token_datasets(args, dataset_dict, device):
     for only when a set holds strings; with already-tokenised rows transformers is never imported."""
     refuse_unsupported(args)
     max_length = view_length(args)
-    tokenize = make_tokenize(resolve_tokenizer(args), max_length) if any(_holds_strings(v) for v in dataset_dict.values()) else None
-    return {k: (None if v is None else DeviceTokenDataset.from_reference(v, device, tokenize, max_length)) for k, v in dataset_dict.items()}
+    tokenizer = resolve_tokenizer(args) if any(_holds_strings(v) for v in dataset_dict.values()) else None
+    tokenize = None if tokenizer is None else make_tokenize(tokenizer, max_length)
+    out = {k: (None if v is None else DeviceTokenDataset.from_reference(v, device, tokenize, max_length)) for k, v in dataset_dict.items()}
+    if out.get("train_ulb") is not None:                                  # what the strong views of this set mask with; checked against the model
+        out["train_ulb"].strong_mask_id = strong_mask_id(args, tokenizer) if device_strong(args) else None
+    return out
 
 
 def build_token_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank, print_fn=print):
@@ -239,9 +339,21 @@ def build_token_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, n
         if dataset_dict.get(name) is None:
             raise ValueError("device_tokens: dataset_dict[%r] is missing or None; the train loaders need a labelled and an unlabelled set (every "
                              "train_step of this project takes x_lb and x_ulb_w)" % name)
-    if "x_ulb_s" in step_keys and dataset_dict["train_ulb"].n_variants == 0:
+    made, ulb = device_strong(args), dataset_dict["train_ulb"]
+    if made and ulb.n_variants:
+        raise ValueError("%s: the unlabelled set carries data_s (pre-augmented variants) and the key asks for strong views made on the device: "
+                         "there must be one source of strong views -- drop data_s or the key" % STRONG_KEY)
+    if "x_ulb_s" in step_keys and ulb.n_variants == 0 and not made:
         raise ValueError("device_tokens: this algorithm's train_step takes x_ulb_s but the unlabelled set has no data_s; " + DATA_S_HELP)
-    return build_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank, TokenTrainLoader, TokenEvalLoader)
+    if not made:
+        return build_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank, TokenTrainLoader, TokenEvalLoader)
+    rate = check_strong_rate(getattr(args, STRONG_RATE_KEY, None))
+    mask_id = getattr(ulb, "strong_mask_id", None)
+    mask_id = strong_mask_id(args) if mask_id is None else mask_id
+    return build_loaders(args, dataset_dict, step_keys, num_train_iter, epochs, num_replicas, rank,
+                         lambda ds, bs, sampler, strong, keys, seed: TokenTrainLoader(ds, bs, sampler, strong=strong, keys=keys, seed=seed,
+                                                                                      device_strong=True, rate=rate, mask_id=mask_id),
+                         TokenEvalLoader)
 
 
 def eval_loader(args, dataset, batch_size, print_fn=print):

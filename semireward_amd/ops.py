@@ -1746,3 +1746,89 @@ def token_view(store, row_off, row_len, src_row, L, pad_id=0, host=None):
     _call("srhip_token_view", _p(store), _p(row_off), _p(row_len), int(row_len.shape[0]), _p(src_row), B, L, int(pad_id), _p(ids), L, _p(key_len),
           _s())
     return ids, key_len
+
+
+TOKEN_COPY, TOKEN_DELETE, TOKEN_MASK, TOKEN_CUTOFF, TOKEN_SWAP = range(5)   # srhip_token_strong ops (srhip.h: SR_TOKEN_*)
+TOKEN_STRONG_MAX_LSRC = 4096                                                # the longest source row srhip_token_strong takes (row and keys share LDS)
+
+
+def token_strong_len(n, op, c):
+    """The length rule of one srhip_token_strong slot: n - c after a DELETE or a CUTOFF, n otherwise (numpy arrays, int64 arithmetic;
+    ``c`` as the slot applies it, i.e. already inside 0 .. max(0, n - 2))."""
+    import numpy as np
+    n, op, c = np.asarray(n, dtype=np.int64), np.asarray(op), np.asarray(c, dtype=np.int64)
+    return np.where((op == TOKEN_DELETE) | (op == TOKEN_CUTOFF), n - c, n)
+
+
+def pack_token_slot(op, c, seed):
+    """(op, c, seed) -> the int64 slot word of srhip_token_strong: bits 0..7 op, bits 8..31 c, bits 32..63 seed."""
+    import numpy as np
+    op, c, seed = (np.asarray(a, dtype=np.int64) for a in (op, c, seed))
+    if op.size and (op.min() < 0 or op.max() > 0xff or c.min() < 0 or c.max() > 0xffffff or seed.min() < 0 or seed.max() > 0xffffffff):
+        raise ValueError("pack_token_slot: op is 8 bits, c 24 bits and seed 32 bits, all unsigned")
+    return (op.astype(np.uint64) | (c.astype(np.uint64) << np.uint64(8)) | (seed.astype(np.uint64) << np.uint64(32))).view(np.int64)
+
+
+def unpack_token_slot(slot):
+    """The inverse of ``pack_token_slot``: (op, c, seed) as int64 arrays."""
+    import numpy as np
+    w = np.ascontiguousarray(slot, dtype=np.int64).view(np.uint64)
+    return tuple(a.astype(np.int64) for a in (w & np.uint64(0xff), (w >> np.uint64(8)) & np.uint64(0xffffff), w >> np.uint64(32)))
+
+
+def check_token_strong(src_row, slots, L, row_len, Lsrc):
+    """The host-side argument check of ``token_strong``: what the kernel would quietly mend is an error here -- a row outside the store (as
+    check_token_rows), an unknown op, a count above the interior its slot meets, an ``L`` (one number, or one per row) below a row's
+    predicted length.  ``slots``: the packed slot words, int64 [2, B].  Returns the predicted lengths int64 [B]."""
+    import numpy as np
+    src_row, slots, row_len = np.asarray(src_row), np.asarray(slots), np.asarray(row_len)
+    if src_row.ndim != 1 or src_row.dtype.kind not in "iu":
+        raise ValueError("token_strong: src_row must be a 1-D integer array, got %s %s" % (src_row.dtype, src_row.shape))
+    if slots.shape != (2, src_row.size) or slots.dtype != np.int64:
+        raise ValueError("token_strong: slots holds the two packed int64 slot words of every row, [2, %d], got %s %s" % (src_row.size, slots.dtype, slots.shape))
+    if not 1 <= int(Lsrc) <= TOKEN_STRONG_MAX_LSRC:
+        raise ValueError("token_strong: Lsrc = %d outside 1 .. %d" % (Lsrc, TOKEN_STRONG_MAX_LSRC))
+    if src_row.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if src_row.min() < 0 or src_row.max() >= len(row_len):
+        raise IndexError("token_strong: src_row outside the store's %d rows" % len(row_len))
+    n = np.minimum(row_len[src_row].astype(np.int64), int(Lsrc))
+    for s in (0, 1):
+        op, c, _ = unpack_token_slot(slots[s])
+        if op.max() > TOKEN_SWAP:
+            raise ValueError("token_strong: slot %d holds op %d, outside 0..4 (copy, delete, mask, cutoff, swap)" % (s, op.max()))
+        ni = np.maximum(n - 2, 0)
+        if (c > ni).any():
+            b = int(np.flatnonzero(c > ni)[0])
+            raise ValueError("token_strong: slot %d of row %d asks for %d of the %d interior tokens it meets" % (s, b, c[b], ni[b]))
+        n = token_strong_len(n, op, c)
+    if (n > np.asarray(L, dtype=np.int64)).any():
+        b = int(np.flatnonzero(n > np.asarray(L, dtype=np.int64))[0])
+        raise ValueError("token_strong: L = %d is below the %d tokens row %d comes out with" % (np.broadcast_to(L, n.shape)[b], n[b], b))
+    return n
+
+
+def token_strong(store, row_off, row_len, src_row, slot0, slot1, L, Lsrc, pad_id=0, mask_id=103, host=None):
+    """The strong view of a batch made from the clean rows of the flat int32 token store (srhip.h: srhip_token_strong): row b is store row
+    ``src_row[b]`` (its first ``Lsrc`` tokens) after the two slots ``slot0[b]``, ``slot1[b]`` (``pack_token_slot``), right-padded with
+    ``pad_id`` to ``L``.  store int32, row_off int64, row_len int32, src_row / slot0 / slot1 int64 [B], all on the device ->
+    (ids int64 [B, L] contiguous, key_len int32 [B]), as ``token_view``.  ``host``: (src_row, slots [2, B], row_len) as numpy arrays, the
+    values the device arrays were copied from, checked before the launch (check_token_strong)."""
+    if store.dtype != torch.int32 or row_off.dtype != torch.int64 or row_len.dtype != torch.int32:
+        raise ValueError("token_strong: the store is int32 with int64 row_off and int32 row_len, got %s / %s / %s" % (store.dtype, row_off.dtype, row_len.dtype))
+    B = int(src_row.shape[0]) if src_row.dim() == 1 else -1
+    if any(t.dtype != torch.int64 or tuple(t.shape) != (B,) for t in (src_row, slot0, slot1)):
+        raise ValueError("token_strong: src_row, slot0 and slot1 are int64 [B], got %s"
+                         % " / ".join("%s %s" % (t.dtype, tuple(t.shape)) for t in (src_row, slot0, slot1)))
+    if row_off.shape != row_len.shape or row_off.dim() != 1:
+        raise ValueError("token_strong: row_off and row_len hold one entry per row")
+    if int(pad_id) < 0 or int(mask_id) < 0:
+        raise ValueError("token_strong: pad_id and mask_id are token ids, got %d and %d" % (pad_id, mask_id))
+    L, Lsrc = int(L), int(Lsrc)
+    if host is not None:
+        check_token_strong(host[0], host[1], L, host[2], Lsrc)
+    ids = torch.empty(B, L, dtype=torch.int64, device=store.device)
+    key_len = torch.empty(B, dtype=torch.int32, device=store.device)
+    _call("srhip_token_strong", _p(store), _p(row_off), _p(row_len), int(row_len.shape[0]), _p(src_row), _p(slot0), _p(slot1), B, Lsrc, L,
+          int(pad_id), int(mask_id), _p(ids), L, _p(key_len), _s())
+    return ids, key_len
