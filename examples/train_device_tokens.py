@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """End-to-end on one MI355X through the library's token input pipeline (``device_tokens: True``): synthetic, already-tokenised sentences (a class
-prefers its own slice of the vocabulary; a handful of distinct lengths), a tiny BERT or BERT-base, SRSoftMatch or SRPseudoLabel.  The rows go in
+prefers its own slice of the vocabulary; four lengths, or every length from 2 to max_length with ``--lengths free``), a tiny BERT or BERT-base, SRSoftMatch or SRPseudoLabel.  The rows go in
 as a plain ``dataset_dict``; the engine packs them into one flat int32 store on the device, builds the reference's sampler stream, and every view
 of a batch -- gather, right-padding to the batch's longest row, the lengths -- is one launch (data/device_tokens.py, csrc/token_view.hip).
 ``alg.train()`` / ``alg.evaluate()`` run with no hand-written batch generator and no tokenizer in the step.
@@ -17,6 +17,8 @@ trains on sentences that have no back-translations.
     python examples/train_device_tokens.py --steps 60 --run-hooks     # the reference's evaluation / checkpoint / logging hooks drive the run
     python examples/train_device_tokens.py --steps 20 --net base      # BERT-base (random init unless a snapshot is on disk), max_length 128
     python examples/train_device_tokens.py --steps 60 --device-strong # SRFlexMatch, strong views made on the device, no data_s
+    python examples/train_device_tokens.py --steps 60 --lengths free  # rows of every length 2 .. max_length: the engine's memory follows the largest batch
+    python examples/train_device_tokens.py --steps 60 --lengths free --bucket 16      # token_len_bucket: padded lengths in multiples of 16
 """
 import argparse
 import os
@@ -31,13 +33,15 @@ from semireward_amd.core.hooks import Hook                   # noqa: E402
 from semireward_amd.nets import bert                         # noqa: E402
 
 CLS, SEP, FIRST = 2, 3, 5                                     # [CLS], [SEP], the first ordinary id of the synthetic vocabulary (4: its [MASK])
-# the engine keeps one set of workspace buffers per distinct (B, L): the lengths stay a handful of values (configs/README.md)
+# 'lengths': the four row lengths of the default; --lengths free draws every row's length from 2 .. max(lengths) (real text: hundreds of
+# distinct padded lengths; the engine's workspaces are sized by the largest batch, configs/README.md)
 NETS = {"tiny": dict(builder=bert.bert_tiny_test, vocab=120, lengths=(8, 16, 24, 32), feature_dim=128, lr=5e-4, mask_id=4),
         "base": dict(builder=bert.bert_base_uncased, vocab=30522, lengths=(32, 64, 96, 128), feature_dim=768, lr=5e-5, mask_id=103)}
 
 
 def synth_rows(n, num_classes, vocab, lengths, seed):
-    """n int32 rows [CLS] w ... [SEP] of one of ``lengths`` tokens: 70 % of the words come from the class's slice of the vocabulary; + labels."""
+    """n int32 rows [CLS] w ... [SEP] of one of ``lengths`` tokens (a range: of any length in it): 70 % of the words come from the class's slice
+    of the vocabulary; + labels."""
     rng = np.random.Generator(np.random.PCG64(seed))
     y = rng.integers(0, num_classes, size=n)
     width = (vocab - FIRST) // num_classes
@@ -84,14 +88,18 @@ def main():
     ap.add_argument("--algorithm", choices=sorted(ALGORITHMS), default=None, help="srsoftmatch; srflexmatch with --device-strong")
     ap.add_argument("--device-strong", action="store_true",
                     help="device_tokens_strong: the strong views are made on the device from the clean sentences, no data_s")
+    ap.add_argument("--lengths", choices=("four", "free"), default="four",
+                    help="free: every row's length is drawn from the whole 2 .. max_length range instead of four values")
+    ap.add_argument("--bucket", type=int, default=None, help="token_len_bucket: padded lengths are rounded up to multiples of this")
     ap.add_argument("--run-hooks", action="store_true",
                     help="run_hooks + device_eval: evaluate and checkpoint every steps / 2 steps (into a temporary save_dir), log every 10")
     a = ap.parse_args()
     a.algorithm = a.algorithm or ("srflexmatch" if a.device_strong else "srsoftmatch")
     C, net = a.classes, NETS[a.net]
-    x_lb, y_lb = synth_rows(10 * C, C, net["vocab"], net["lengths"], 1)
-    x_ulb, _ = synth_rows(512, C, net["vocab"], net["lengths"], 2)
-    x_te, y_te = synth_rows(128, C, net["vocab"], net["lengths"], 3)
+    lengths = range(2, max(net["lengths"]) + 1) if a.lengths == "free" else net["lengths"]
+    x_lb, y_lb = synth_rows(10 * C, C, net["vocab"], lengths, 1)
+    x_ulb, _ = synth_rows(512, C, net["vocab"], lengths, 2)
+    x_te, y_te = synth_rows(128, C, net["vocab"], lengths, 3)
     ulb = {"data": x_ulb, "targets": None}
     if a.algorithm != "srpseudolabel" and not a.device_strong:   # its train_step takes x_ulb_s: two variants per sentence
         rng = np.random.Generator(np.random.PCG64(4))
@@ -105,7 +113,7 @@ def main():
         dataset="synthetic_tokens", max_length=max(net["lengths"]), batch_size=a.batch, uratio=1, eval_batch_size=16,
         train_sampler="RandomSampler", device_tokens=True, device_tokens_strong=a.device_strong, device_tokens_mask_id=net["mask_id"],
         dataset_dict={"train_lb": {"data": x_lb, "targets": y_lb}, "train_ulb": ulb, "eval": {"data": x_te, "targets": y_te}},
-        **ALGORITHMS[a.algorithm])
+        **({} if a.bucket is None else dict(token_len_bucket=a.bucket)), **ALGORITHMS[a.algorithm])
     if a.run_hooks:
         with tempfile.TemporaryDirectory() as save_dir:
             vars(args).update(run_hooks=True, device_eval=True, num_eval_iter=max(steps // 2, 1), num_log_iter=10, save_dir=save_dir,

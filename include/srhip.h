@@ -721,6 +721,16 @@ int srhip_embed_ln_bwd(const float* dy, const long long* ids, int ld_ids, const 
                        const float* type0, const float* mean, const float* rstd, const float* gamma, float* dword, float* dpos, float* dtype0,
                        float* dgamma, float* dbeta, int B, int L, int D, int pad_id, unsigned drop_key, unsigned drop_thresh, float drop_scale,
                        void* stream);
+/* The same backward with ONE summation order: two launches and no atomics (csrc/enc_ops.hip) -- every table row is summed over the token rows
+ * that hold its id in row order, every position over the sequences in order, dgamma / dbeta / dtype0 over workgroups of 32 rows in order.  Equal
+ * inputs give equal bits, and a row whose upstream gradient is exactly zero changes no bit whatever id it holds.  ws: scratch of
+ * srhip_embed_ln_bwd_ws_floats(B, L, D) floats, 16-byte aligned, nothing kept between calls.  SR_EINVAL as srhip_embed_ln_bwd, and a null or
+ * misaligned ws. */
+long srhip_embed_ln_bwd_ws_floats(int B, int L, int D);
+int srhip_embed_ln_bwd_ordered(const float* dy, const long long* ids, int ld_ids, const int* seq_index, const float* word, const float* pos,
+                               const float* type0, const float* mean, const float* rstd, const float* gamma, float* dword, float* dpos,
+                               float* dtype0, float* dgamma, float* dbeta, float* ws, int B, int L, int D, int pad_id, unsigned drop_key,
+                               unsigned drop_thresh, float drop_scale, void* stream);
 int srhip_postln_fwd(const float* y, const float* gamma, const float* beta, float eps, float* x, void* x_bf16, float* mean, float* rstd, int M,
                      int D, void* stream);
 int srhip_postln_bwd(const float* dy, const float* y, const float* mean, const float* rstd, const float* gamma, float* dx, void* dx_bf16,
@@ -903,6 +913,26 @@ enum { SR_TOKEN_STRONG_MAX_LSRC = 4096 };
 int srhip_token_strong(const int* store, const long long* row_off, const int* row_len, int n_rows, const long long* src_row,
                        const long long* slot0, const long long* slot1, int B, int Lsrc, int L, int pad_id, int mask_id, long long* ids,
                        int ld_ids, int* key_len, void* stream);
+
+/* ---- the views of one step joined into one token batch (nets/bert.py TokenBatch.cat with unequal padded lengths, ``token_len_bucket``),
+ * one launch.  tests/_token_cat_cases.py restates it (token_cat_ref).
+ *   src      HOST array of n_src (1 .. 4) sources, copied into the kernel's arguments: ids int64 [S, L] contiguous (8-byte aligned),
+ *            key_len int32 [S], seq_len int32 [S] or NULL, all on the device
+ *   ids      int64 [sum S, L_out] contiguous, L_out >= every source's L;  key_len, seq_len int32 [sum S]
+ * Output row b is row r of source j (sources in order, their rows in order): ids[b, t] = src[j].ids[r, t] for t < L_j, pad_id for
+ * L_j <= t < L_out; key_len[b] = src[j].key_len[r]; seq_len[b] = src[j].seq_len[r] when the source has one, else L_j.  16-byte loads and
+ * stores where the source row and the output row are both 16-byte aligned, 8-byte ones otherwise; the pair that holds a row's end is peeled:
+ * nothing past a source row is read, nothing past an output row written.  One workgroup per output row, no LDS, no atomics, no
+ * synchronisation, no allocation: it can be captured in a graph.  SR_EINVAL: a null pointer (seq_len of a source excepted), n_src outside
+ * 1 .. 4, an S or L <= 0, an L above L_out, sum S > 65535, ids (source or output) not 8-byte aligned, a negative pad_id. */
+enum { SR_TOKEN_CAT_MAX_SRC = 4 };
+typedef struct {
+  const long long* ids;
+  const int* key_len;
+  const int* seq_len;
+  int S, L;
+} srhip_token_src;
+int srhip_token_cat(const srhip_token_src* src, int n_src, int pad_id, long long* ids, int L_out, int* key_len, int* seq_len, void* stream);
 
 /* ---- WideResNet building blocks (classic_cv backbone, semilearn/nets/wrn/wrn.py; BASELINE.json configs[0], parity configuration) ----
  * Feature maps are NHWC = row-major [rows = B*H*W, C].  conv = im2col (bf16) + srhip_gemm_nt; dW = srhip_gemm_tn_grouped_f32(dY, col);

@@ -165,6 +165,8 @@ SIGNATURES = {
     "srhip_attn_masked_bwd": (I, [P, P, P, P, P, P, P, I, I, I, F, U, U, F, P]),
     "srhip_embed_ln_fwd": (I, [P, I, P, P, P, P, P, P, F, P, P, P, P, I, I, I, U, U, F, P]),
     "srhip_embed_ln_bwd": (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, U, U, F, P]),
+    "srhip_embed_ln_bwd_ws_floats": (L, [I, I, I]),
+    "srhip_embed_ln_bwd_ordered": (I, [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, U, U, F, P]),
     "srhip_postln_fwd": (I, [P, P, P, F, P, P, P, P, I, I, P]),
     "srhip_postln_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, U, U, F, P]),
     "srhip_postln_bwd_part": (I, [P, P, P, P, P, P, P, P, I, I, I, U, U, F, P]),
@@ -180,6 +182,7 @@ SIGNATURES = {
     "srhip_wave_effect": (I, [P, P, P, I, P, P, P, P, I, P, I, P, P, P, P, P]),
     "srhip_token_view": (I, [P, P, P, I, P, I, I, I, P, I, P, P]),
     "srhip_token_strong": (I, [P, P, P, I, P, P, P, I, I, I, I, I, P, I, P, P]),
+    "srhip_token_cat": (I, [P, I, I, P, I, P, P, P]),
     "srhip_gemm_nt_dropout": (I, [I, P, I, P, I, P, I, I, I, I, P, P, P, I, U, U, F, P]),
     "srhip_w2v_conv0": (I, [I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P]),
     "srhip_w2v_conv_weight_prep": (I, [P, P, P, I, I, I, P]),
@@ -203,6 +206,11 @@ class DwTail(ctypes.Structure):
     """srhip_dw_tail (include/srhip.h): the small launches that ride behind the tiles of srhip_gemm_tn_grouped_tail_f32."""
     _fields_ = [(n, c_void_p) for n in ("ln_desc", "ln_part", "dlogits", "feat", "dWh", "dbh", "dx", "img", "img_index", "dpos", "dcls",
                                          "pe_ws")] + [(n, c_int) for n in ("n_ln", "n_rep", "C", "B", "D", "in_chans", "HW", "ps")]
+
+
+class TokenSrc(ctypes.Structure):
+    """srhip_token_src (include/srhip.h): one source of srhip_token_cat."""
+    _fields_ = [("ids", c_void_p), ("key_len", c_void_p), ("seq_len", c_void_p), ("S", c_int), ("L", c_int)]
 
 
 def lib():

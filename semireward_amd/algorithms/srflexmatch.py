@@ -704,8 +704,11 @@ class SRConsistencyBase(AlgorithmBase):
         return x if isinstance(x, TokenBatch) else TokenBatch.from_dict(x, self.device)
 
     def _token_cat(self, batches):
+        """The views of a step as one batch: one srhip_token_cat launch into the model's grow-only buffer when their padded lengths differ or
+        ``token_len_bucket`` rounds them up (nets/bert.py TokenBatch.cat); views of one length and no bucket are concatenated as they are."""
         from ..nets.bert import TokenBatch
-        return TokenBatch.cat(batches)
+        m = self.model
+        return TokenBatch.cat(batches, bucket=self.token_len_bucket, max_pos=m.cfg.max_pos, pad_id=m.cfg.pad_id, out=m.token_cat_out)
 
     def _make_plan(self, nl, nu, K, defer_fraction=None):
         mk = lambda whole: _Plan.cat_passes(nl, nu, K, self.device, extra_pass0_strong=self.fairness_rows and K > 0,    # noqa: E731

@@ -11,6 +11,7 @@ Datasets / loaders are the reference's own (CPU input pipeline): ``set_dataset``
 ``get_data_loader`` when semilearn is importable (or take ready dicts from ``args``); ``train()`` then zips ``loader_dict['train_lb'/'train_ulb']``
 as the reference does, or consumes any iterable of (data_lb, data_ulb) handed in.
 """
+import numbers
 import os
 from collections import OrderedDict
 from inspect import signature
@@ -62,6 +63,16 @@ class DeferredScalar:
     def __hash__(self): return id(self)
 
 
+def check_token_len_bucket(v):
+    """The yaml key ``token_len_bucket``: absent / None -> None (today's lengths); else a positive integer (bools and strings are refused)."""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or int(v) < 1:
+        raise ValueError("token_len_bucket: a positive integer (padded lengths are rounded up to its multiples, capped by the model's "
+                         "positions), got %r" % (v,))
+    return int(v)
+
+
 class AlgorithmBase:
     def __init__(self, args, net_builder, tb_log=None, logger=None, **kwargs):
         self.args = args
@@ -105,6 +116,7 @@ class AlgorithmBase:
         self.device_data = bool(g("device_data", False))     # dataset arrays resident in HBM, loaders of data/device_loader.py
         self.device_audio = bool(g("device_audio", False))   # waveform clips resident in HBM, loaders of data/device_audio.py (usb_audio)
         self.device_tokens = bool(g("device_tokens", False)) # token rows resident in HBM, loaders of data/device_tokens.py (usb_nlp)
+        self.token_len_bucket = check_token_len_bucket(g("token_len_bucket"))     # usb_nlp: padded lengths rounded up to a multiple (None: as they come)
         self.device_eval = bool(g("device_eval", False))     # evaluate() accumulates loss and confusion matrix on the device (csrc/eval.hip)
         self.run_hooks = bool(g("run_hooks", False))         # the reference's EvaluationHook / CheckpointHook / LoggingHook join the hook list
         monitor = bool(g("monitor_pseudo_labels", False))    # per-step pseudo-label quality counters on the device (core/pl_monitor.py)
@@ -129,6 +141,11 @@ class AlgorithmBase:
         self.model = self.set_model()
         if self.input_mode is not None:      # refusals decided from the model: another kind of backbone; tokens: max_length beyond max_pos, a stored id beyond the vocabulary
             self.input_mode.refuse_unsupported_model(self.model, self.dataset_dict)
+        if self.token_len_bucket and not self.model.takes_tokens:
+            raise ValueError("token_len_bucket: %d buckets the padded length of token batches; this backbone (%s) does not take token batches "
+                             "(drop the key)" % (self.token_len_bucket, type(self.model).__name__))
+        if self.device_tokens and self.loader_dict is not None:
+            self._reserve_token_arenas()
         if self.model.couples_batch_rows:
             self.model.dp = self.dp          # BatchNorm backbone under data parallel = SyncBatchNorm, as the reference's send_model_cuda (misc.py:55)
         self.ema_model = self.set_ema_model()
@@ -390,6 +407,27 @@ class AlgorithmBase:
         finally:
             net.training = was_training
 
+    def _reserve_token_arenas(self):
+        """device_tokens: the engine's arenas are sized once, for the largest batch the train loaders can produce -- every sequence of a step
+        (labelled + weak + strong) at the longest stored row, bucketed and capped like the batches themselves -- so a run never regrows them."""
+        n_seq = longest = 0
+        for name in ("train_lb", "train_ulb"):
+            ld = self.loader_dict.get(name)
+            if ld is None or not hasattr(getattr(ld, "dataset", None), "row_len_host"):
+                continue
+            n_seq += ld.batch_size * sum(1 for k in ld.keys if k.startswith("x_"))
+            longest = max(longest, int(ld.dataset.row_len_host.max()))
+        if n_seq:
+            max_pos = self.model.cfg.max_pos          # a bucket is capped by the positions, not by max_length (40 tokens in buckets of 16: 48)
+            cap = min(int(getattr(self.args, "max_length", 0) or max_pos), max_pos)
+            self.model.reserve_tokens(n_seq, ops.token_len_bucket(min(longest, cap), self.token_len_bucket, max_pos))
+
+    def _bucket_tokens(self, x, net):
+        """``token_len_bucket``: an evaluation / scoring batch of the token engine padded to its bucket (a cat of one source); else ``x``."""
+        if not self.token_len_bucket or not hasattr(x, "key_len"):
+            return x
+        return type(x).cat([x], bucket=self.token_len_bucket, max_pos=net.cfg.max_pos, pad_id=net.cfg.pad_id, out=net.token_cat_out)
+
     def _eval_batches(self, net, loader):
         """(logits, labels) of every batch of ``loader`` on the device: the inference forward of the training path."""
         for data in loader:
@@ -402,7 +440,7 @@ class AlgorithmBase:
             else:
                 x = x.to(self.device, non_blocking=True).contiguous()
             y = data["y_lb"].to(self.device, non_blocking=True).contiguous()
-            lg, _, _ = net.forward_features(x, None, None, save=False)
+            lg, _, _ = net.forward_features(self._bucket_tokens(x, net), None, None, save=False)
             yield lg, y
 
     def _evaluate_on_host(self, net, loader, eval_dest, return_logits):

@@ -200,7 +200,7 @@ def score_loader(alg, net, loader, n, reward_group):
     with ops.stream_scope():
         for data in loader:
             x, idx = _batch_rows(alg, data)
-            lg, feat, _ = net.forward_features(x, None, None, save=False)
+            lg, feat, _ = net.forward_features(alg._bucket_tokens(x, net), None, None, save=False)
             B = int(lg.shape[0])
             if scratch is None or scratch.rows < B:
                 scratch = _Scratch(B, alg.device)

@@ -139,6 +139,148 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const float* __restri
   }
 }
 
+// ---- the same backward with ONE summation order (srhip_embed_ln_bwd_ordered): equal inputs give equal bits, and a row whose upstream gradient
+// is exactly zero (the filler rows of a joined / bucketed token batch) changes no bit whatever id it holds.  Two launches (rows; then word,
+// pos and fold side by side), no atomics:
+//   rows     dropout' -> LayerNorm' per token row: e[row, :] and the row's id go to scratch, the workgroup's partial sums of dgamma / dbeta /
+//            dtype0 (its 32 rows, in row order) to one slot per workgroup
+//   word     one wave per token row: the FIRST row that holds an id (no earlier row does) owns that id's table row -- it adds its own e and
+//            the e of every later row with the id, in row order, then adds the sum to dword (no other wave touches that table row)
+//   pos      one workgroup per position: dpos[p] += e[0 L + p] + e[1 L + p] + ..., sequences in order
+//   fold     dgamma / dbeta / dtype0 += the workgroups' partial sums: four interleaved chains in workgroup order, joined by a fixed tree
+template <int NV>
+__global__ __launch_bounds__(256) void embed_ln_bwd_rows_kernel(const float* __restrict__ dy, const long long* __restrict__ ids, int ld_ids,
+                                                               const int* __restrict__ seq_index, const float* __restrict__ word,
+                                                               const float* __restrict__ pos, const float* __restrict__ type0,
+                                                               const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                               const float* __restrict__ gamma, float* __restrict__ e,
+                                                               int* __restrict__ rid, float* __restrict__ part, int B, int L, Drop dr) {
+  constexpr int D = NV * 128;
+  __shared__ float red[3][4][D];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, M = B * L;
+  float2 ag[NV], ab[NV], at[NV], g[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    ag[i] = ab[i] = at[i] = make_float2(0.f, 0.f);
+    g[i] = reinterpret_cast<const float2*>(gamma)[i * 64 + lane];
+  }
+  for (int rr = 0; rr < 8; ++rr) {
+    const int row = blockIdx.x * 32 + wave * 8 + rr;
+    if (row >= M) break;
+    const int b = row / L, p = row - b * L;
+    const long long id = ids[(size_t)(seq_index ? seq_index[b] : b) * ld_ids + p];
+    if (lane == 0) rid[row] = (int)id;
+    const float2* wr = reinterpret_cast<const float2*>(word + (size_t)id * D);
+    const float2* pr = reinterpret_cast<const float2*>(pos + (size_t)p * D);
+    const float2* tr = reinterpret_cast<const float2*>(type0);
+    const float2* dr_ = reinterpret_cast<const float2*>(dy + (size_t)row * D);
+    const float mu = mean[row], rs = rstd[row];
+    float2 xh[NV], dh[NV];
+    float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const float2 a = wr[i * 64 + lane], c = pr[i * 64 + lane], t = tr[i * 64 + lane];
+      xh[i] = make_float2((a.x + c.x + t.x - mu) * rs, (a.y + c.y + t.y - mu) * rs);
+      const float2 d = drop2(dr_[i * 64 + lane], (uint32_t)row * D + 2 * (i * 64 + lane), dr);
+      ag[i].x += d.x * xh[i].x; ag[i].y += d.y * xh[i].y;
+      ab[i].x += d.x; ab[i].y += d.y;
+      dh[i] = make_float2(d.x * g[i].x, d.y * g[i].y);
+      c1 += dh[i].x + dh[i].y;
+      c2 += dh[i].x * xh[i].x + dh[i].y * xh[i].y;
+    }
+    c1 = wave_sum(c1) * (1.0f / D);
+    c2 = wave_sum(c2) * (1.0f / D);
+    float2* er = reinterpret_cast<float2*>(e + (size_t)row * D);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const float2 ev = make_float2(rs * (dh[i].x - c1 - xh[i].x * c2), rs * (dh[i].y - c1 - xh[i].y * c2));
+      er[i * 64 + lane] = ev;
+      at[i].x += ev.x; at[i].y += ev.y;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = 2 * (i * 64 + lane);
+    red[0][wave][c] = ag[i].x; red[0][wave][c + 1] = ag[i].y;
+    red[1][wave][c] = ab[i].x; red[1][wave][c + 1] = ab[i].y;
+    red[2][wave][c] = at[i].x; red[2][wave][c + 1] = at[i].y;
+  }
+  __syncthreads();
+  float* pb = part + (size_t)blockIdx.x * 3 * D;
+  for (int c = threadIdx.x; c < D; c += 256) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) pb[q * D + c] = red[q][0][c] + red[q][1][c] + red[q][2][c] + red[q][3][c];
+  }
+}
+
+// word | pos | fold in ONE launch: workgroups [0, nw) take four token rows each (one per wave), [nw, nw + L) a position each, the last
+// 3 D / 64 a 64-column slice of one of dgamma / dbeta / dtype0.  The ids are scanned 256 at a time (four independent coalesced loads), so a
+// wave waits for M / 256 round trips, not M / 64.
+template <int NV>
+__global__ __launch_bounds__(256) void embed_scatter_ordered_kernel(const float* __restrict__ e, const int* __restrict__ rid,
+                                                                   const float* __restrict__ part, int nblk, float* __restrict__ dword,
+                                                                   float* __restrict__ dpos, float* __restrict__ dgamma,
+                                                                   float* __restrict__ dbeta, float* __restrict__ dtype0, int B, int L,
+                                                                   int pad_id, int nw) {
+  constexpr int D = NV * 128;
+  __shared__ float red[4][64];
+  const int M = B * L, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if ((int)blockIdx.x >= nw + L) {                          // ---- fold: the workgroups' partial sums, four interleaved chains, fixed tree
+    const int t = blockIdx.x - nw - L, q = t / (D / 64), c = (t - q * (D / 64)) * 64 + lane;
+    float s = 0.f;
+    for (int k = wave; k < nblk; k += 4) s += part[((size_t)k * 3 + q) * D + c];
+    red[wave][lane] = s;
+    __syncthreads();
+    if (wave == 0) {
+      float* out = q == 0 ? dgamma : (q == 1 ? dbeta : dtype0);
+      out[c] += (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    }
+    return;
+  }
+  if ((int)blockIdx.x >= nw) {                              // ---- pos: the sequences in order
+    const int p = blockIdx.x - nw;
+    for (int c = threadIdx.x; c < D; c += 256) {
+      float s = 0.f;
+      for (int b = 0; b < B; ++b) s += e[((size_t)b * L + p) * D + c];
+      dpos[(size_t)p * D + c] += s;
+    }
+    return;
+  }
+  const int row = blockIdx.x * 4 + wave;                    // ---- word: one wave per token row, no barrier on this path
+  if (row >= M) return;
+  const int id = rid[row];
+  if (id == pad_id) return;                                 // nn.Embedding(padding_idx): no gradient for [PAD]
+  for (int j = 0; j < row; j += 256) {                      // an earlier row with this id owns the table row
+    bool h = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const int x = j + k * 64 + lane; h |= x < row && rid[x] == id; }
+    if (__ballot(h)) return;
+  }
+  float2 acc[NV];
+  const float2* er = reinterpret_cast<const float2*>(e + (size_t)row * D);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) acc[i] = er[i * 64 + lane];
+  for (int j = (row + 1) & ~255; j < M; j += 256) {
+    int v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const int x = j + k * 64 + lane; v[k] = (x > row && x < M) ? rid[x] : -1; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      unsigned long long hit = __ballot(v[k] == id);
+      while (hit) {                                         // the later rows with this id, in row order
+        const int b = __ffsll((long long)hit) - 1;
+        hit &= hit - 1;
+        const float2* xr = reinterpret_cast<const float2*>(e + (size_t)(j + k * 64 + b) * D);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) { const float2 u = xr[i * 64 + lane]; acc[i].x += u.x; acc[i].y += u.y; }
+      }
+    }
+  }
+  float2* wg = reinterpret_cast<float2*>(dword + (size_t)id * D);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) { float2 u = wg[i * 64 + lane]; u.x += acc[i].x; u.y += acc[i].y; wg[i * 64 + lane] = u; }
+}
+
 // ---- post-LN forward: x = LayerNorm(y) in fp32 (residual stream of the next sub-layer) and bf16 (its GEMM operand) ------------
 // (two rows per wave, every load requested before the first reduction: see ln_fwd_kernel in vit_ops.hip; x may alias y -- a wave reads
 // both of its rows before it writes either)
@@ -346,6 +488,35 @@ extern "C" int srhip_embed_ln_bwd(const float* dy, const long long* ids, int ld_
   hipStream_t s = (hipStream_t)stream;
 #define CALL(NV) SR_LAUNCH(embed_ln_bwd_kernel<NV>, dim3(cdiv((long)B * L, 32)), dim3(256), 0, s, dy, ids, ld_ids, seq_index, word, pos, \
                                     type0, mean, rstd, gamma, dword, dpos, dtype0, dgamma, dbeta, B, L, pad_id, dr)
+  DISPATCH_NV(D, CALL)
+#undef CALL
+  SR_CHECK_LAUNCH();
+  return SR_OK;
+}
+
+extern "C" long srhip_embed_ln_bwd_ws_floats(int B, int L, int D) {
+  const long M = (long)B * L;                               // e [M, D] | the workgroups' partial sums [ceil(M / 32), 3, D] | the rows' ids [M] (room for 2 M)
+  return M * D + (long)cdiv(M, 32) * 3 * D + 2 * M;
+}
+
+extern "C" int srhip_embed_ln_bwd_ordered(const float* dy, const long long* ids, int ld_ids, const int* seq_index, const float* word,
+                                          const float* pos, const float* type0, const float* mean, const float* rstd, const float* gamma,
+                                          float* dword, float* dpos, float* dtype0, float* dgamma, float* dbeta, float* ws, int B, int L, int D,
+                                          int pad_id, unsigned drop_key, unsigned drop_thresh, float drop_scale, void* stream) {
+  if (!dy || !ids || !mean || !rstd || !dword || !dpos || !dtype0 || !dgamma || !dbeta || !ws || B <= 0 || L <= 0) return SR_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(ws) & 15) || (D != 128 && D != 384 && D != 768)) return SR_EINVAL;
+  const Drop dr{drop_key, drop_thresh, drop_scale};
+  hipStream_t s = (hipStream_t)stream;
+  const int M = B * L, nblk = cdiv(M, 32);
+  float* e = ws;
+  float* part = e + (size_t)M * D;
+  int* rid = reinterpret_cast<int*>(part + (size_t)nblk * 3 * D);                   // (the ids of a table of at most 2^31 rows)
+  const int nw = cdiv(M, 4);
+#define CALL(NV)                                                                                                                          \
+  SR_LAUNCH(embed_ln_bwd_rows_kernel<NV>, dim3(nblk), dim3(256), 0, s, dy, ids, ld_ids, seq_index, word, pos, type0, mean, rstd, gamma, e, \
+            rid, part, B, L, dr);                                                                                                         \
+  SR_LAUNCH(embed_scatter_ordered_kernel<NV>, dim3(nw + L + 3 * (D / 64)), dim3(256), 0, s, e, rid, part, nblk, dword, dpos, dgamma, dbeta, \
+            dtype0, B, L, pad_id, nw)
   DISPATCH_NV(D, CALL)
 #undef CALL
   SR_CHECK_LAUNCH();

@@ -110,20 +110,40 @@ class TokenBatch:
         return {"input_ids": self.ids, "attention_mask": mask}
 
     @classmethod
-    def cat(cls, batches):
+    def cat(cls, batches, bucket=None, max_pos=None, pad_id=0, out=None):
         """One batch out of several (x_lb, x_ulb_w, x_ulb_s of one step; the reference forwards them in separate model calls under
-        use_cat=False, each padded to its own longest row).  Shorter batches are filled up to the longest L with [PAD]."""
+        use_cat=False, each padded to its own longest row).  Batches of one padded length without a ``bucket`` are concatenated as they are
+        (seq_len stays None).  Otherwise ONE srhip_token_cat launch fills every row up to L_out with ``pad_id`` and writes seq_len, each
+        row's own padded length: L_out is the longest L, or with ``bucket`` (``token_len_bucket``) min(ceil(L / bucket) * bucket, max_pos)
+        -- a single batch is a cat of one source.  ``out``: a TokenCatBuffer the three outputs are views of (nothing is allocated once it
+        has met the largest batch; the result is valid until the next cat into it)."""
+        batches = list(batches)
         L = max(b.L for b in batches)
-        kl = torch.cat([b.key_len for b in batches]).contiguous()
-        if all(b.L == L and b.seq_len is None for b in batches):
-            return cls(torch.cat([b.ids for b in batches]).contiguous(), kl)
-        ids = torch.zeros(sum(b.S for b in batches), L, dtype=torch.int64, device=kl.device)
-        sl, r = [], 0
-        for b in batches:
-            ids[r:r + b.S, :b.L] = b.ids
-            sl.append(b.seq_len if b.seq_len is not None else torch.full((b.S,), b.L, dtype=torch.int32, device=kl.device))
-            r += b.S
-        return cls(ids, kl, torch.cat(sl).contiguous())
+        if not bucket and all(b.L == L and b.seq_len is None for b in batches):
+            return cls(torch.cat([b.ids for b in batches]).contiguous(), torch.cat([b.key_len for b in batches]).contiguous())
+        if bucket and max_pos is None:
+            raise ValueError("TokenBatch.cat: a bucket needs max_pos, the length no batch may exceed")
+        L_out = ops.token_len_bucket(L, bucket, max_pos)
+        ids, kl, sl = ops.token_cat([(b.ids, b.key_len, b.seq_len) for b in batches], L_out, pad_id,
+                                    out=None if out is None else out.take(sum(b.S for b in batches), L_out))
+        return cls(ids, kl, sl)
+
+
+class TokenCatBuffer:
+    """Grow-only storage of ``TokenBatch.cat``'s outputs on one device: ``take(S, L)`` returns (ids int64 [S, L], key_len int32 [S], seq_len
+    int32 [S]) as leading views of the largest allocation made so far, every ids row as aligned as a fresh tensor's."""
+
+    def __init__(self, device):
+        self.device, self.ids, self.lens = torch.device(device), None, None
+
+    def take(self, S, L):
+        if self.ids is None or self.ids.numel() < S * L:
+            self.ids = None
+            self.ids = torch.empty(S * L, dtype=torch.int64, device=self.device)
+        if self.lens is None or self.lens.shape[1] < S:
+            self.lens = None
+            self.lens = torch.empty(2, S, dtype=torch.int32, device=self.device)
+        return self.ids[:S * L].view(S, L), self.lens[0, :S], self.lens[1, :S]
 
 
 class ClassificationBert(PostLNEncoderMixin):
@@ -140,6 +160,7 @@ class ClassificationBert(PostLNEncoderMixin):
         self.enc_p = dict(attn=cfg.p_drop, hidden=cfg.p_drop, act=0.0)
         self._rng_calls, self.seed = 0, 0
         self.inject_seed = None                       # tests: the 64-bit dropout seed of the next forward calls
+        self.token_cat_out = TokenCatBuffer(self.device)     # where TokenBatch.cat joins a step's views (the algorithms' _token_cat)
 
     def enc_names(self, i):
         p = _layer(i)
@@ -197,16 +218,43 @@ class ClassificationBert(PostLNEncoderMixin):
         return ((self.seed & 0xFFFFFFFF) << 32) + self._rng_calls
 
     # ---- forward ----------------------------------------------------------------------------------------
+    def _ctx_arena(self, tag, rows=0, seqs=0):
+        a = self._arenas.get(("ctx", tag))
+        if a is None:
+            a = self._arena(("ctx", tag), self.enc_ctx_spec() + [("st0", 1, "row", 2, torch.float32)], rows, seqs)
+            a.views = {}                                     # (B, L) -> the view set; void when the arena is replaced
+            a.on_release.append(a.views.clear)
+        else:
+            a.reserve(max(rows, self._reserved[0]), max(seqs, self._reserved[1]))
+        return a
+
     def _ctx_buffers(self, B, L, tag):
-        key = ("ctx", B, L, tag)
-        if key in self._buf_cache:
-            return self._buf_cache[key]
-        c = types.SimpleNamespace()
-        self.enc_alloc_ctx(c, B, L)
-        self.head_alloc_ctx(c, B)
-        c.st0 = torch.empty(2, B * L, dtype=torch.float32, device=self.device)
-        self._buf_cache[key] = c
+        """The saved context of a save=True forward at (B, L): views of the first B * L rows of the grow-only arena of ``tag`` (nets/surface.py
+        RowArena) -- memory follows the largest batch met, not the number of distinct padded lengths.  Two contexts that are alive at the same
+        time need two tags: they would share the arena's rows."""
+        a = self._ctx_arena(tag, B * L, B)
+        c = a.views.get((B, L))
+        if c is None:
+            if len(a.views) >= 64:                           # host objects only: the oldest view set goes
+                a.views.pop(next(iter(a.views)))
+            c = a.views[(B, L)] = types.SimpleNamespace(arena=a)
+            self.enc_view_ctx(c, a, B, L)
+            c.st0 = a.view("st0", 0, (2, B * L))
         return c
+
+    def reserve_tokens(self, n_seq, L, tags=("",)):
+        """Room for batches of up to ``n_seq`` sequences padded to ``L`` in every arena and rows-capacity workspace: the saved context of ``tags``
+        and of every tag met so far, their output-gradient buffers, and whatever is made later starts at this size.  A run that reserves its
+        largest batch up front (``set_data_loader`` with ``device_tokens``) never regrows: ``arena_allocations`` stays put."""
+        n_seq, L = int(n_seq), int(L)
+        if n_seq < 1 or not 1 <= L <= self.cfg.max_pos:
+            raise ValueError("reserve_tokens: n_seq >= 1 sequences of 1 .. %d (max_pos) tokens, got %d x %d" % (self.cfg.max_pos, n_seq, L))
+        self._reserved = (max(self._reserved[0], n_seq * L), max(self._reserved[1], n_seq))
+        self.token_cat_out.take(n_seq, L)
+        for tag in tags:                                     # the context arena and, through its plan, the output-gradient arena
+            self.enc_bwd_arena(n_seq * L, self._ctx_buffers(n_seq, L, tag))
+        for a in list(self._arenas.values()):
+            a.reserve(*((self._reserved[0], 0) if not any(s[2] == "seq" for s in a.spec) else self._reserved))
 
     def forward_features(self, tok, seq_index=None, droppath=None, save=False, B=None, seed="auto", tag="", buftag=""):
         """tok: TokenBatch; seq_index int32 [B] (optional gather of sequences: lets the K+1 passes of one SemiReward step share one
@@ -226,13 +274,13 @@ class ClassificationBert(PostLNEncoderMixin):
         t = ("s" if save else "i") + buftag
         dr = (lambda site, p=cfg.p_drop: ops.Drop(seed, site, p) if p > 0 else None) if seed is not None else (lambda site, p=0.0: None)
         ctx = None
-        x = self._buf(t + "x", (M, D), f32)
+        x = self._buf_rows(t + "x", (M, D), f32, M)
         if save:
             ctx = self._ctx_buffers(B, L, tag)
             ctx.B, ctx.L, ctx.tok, ctx.seq_index, ctx.key_len, ctx.seq_len, ctx.seed = B, L, tok, seq_index, key_len, seq_len, seed
             xb = ctx.xb[0]
         else:
-            xb = self._buf(t + "xb", (M, D), bf16)
+            xb = self._buf_rows(t + "xb", (M, D), bf16, M)
         ops.embed_ln_fwd(tok.ids, seq_index, P(E + "word_embeddings.weight"), P(E + "position_embeddings.weight"),
                          P(E + "token_type_embeddings.weight"), P(E + "LayerNorm.weight"), P(E + "LayerNorm.bias"), cfg.eps, x, xb,
                          ctx.st0[0] if save else None, ctx.st0[1] if save else None, B, L, D, dr(SITE_EMB))
@@ -261,13 +309,17 @@ class ClassificationBert(PostLNEncoderMixin):
         M = B * L
         dr = (lambda site, p=cfg.p_drop: ops.Drop(seed, site, p) if p > 0 else None) if seed is not None else (lambda site, p=0.0: None)
         P, G = self.p, (lambda n: self.p(n, self.grad))
-        dx = self._buf("b_dx", (M, D), torch.float32)
+        dx = self._buf_rows("b_dx", (M, D), torch.float32, M)
         self.head_backward(ctx, dlogits, dx, B, L, dr(SITE_HEAD, cfg.p_head), ctx.seq_len)
         self.enc_backward(dx, ctx, B, L, ctx.key_len, dr)
-        ops.embed_ln_bwd(dx, ctx.tok.ids, ctx.seq_index, P(E + "word_embeddings.weight"), P(E + "position_embeddings.weight"),
+        # one summation order for the three tables and the embedding LayerNorm (no fp32 atomics): equal bits for equal inputs, and the
+        # filler rows of a joined / bucketed batch change no bit whatever ids they hold
+        nws = M * D + (M + 31) // 32 * 3 * D + 2 * M            # = ops.embed_ln_bwd_ws_floats(B, L, D)
+        ws = self._buf_rows("b_embws", (nws,), torch.float32, M)
+        ops.embed_ln_bwd_ordered(dx, ctx.tok.ids, ctx.seq_index, P(E + "word_embeddings.weight"), P(E + "position_embeddings.weight"),
                          P(E + "token_type_embeddings.weight"), ctx.st0[0], ctx.st0[1], P(E + "LayerNorm.weight"),
                          G(E + "word_embeddings.weight"), G(E + "position_embeddings.weight"), G(E + "token_type_embeddings.weight"),
-                         G(E + "LayerNorm.weight"), G(E + "LayerNorm.bias"), B, L, D, cfg.pad_id, dr(SITE_EMB))
+                                 G(E + "LayerNorm.weight"), G(E + "LayerNorm.bias"), ws, B, L, D, cfg.pad_id, dr(SITE_EMB))
 
 
 # ---- builders with the reference's names (bert.py:62-69) --------------------------------------------------------------------------------

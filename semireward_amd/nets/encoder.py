@@ -60,6 +60,28 @@ class PostLNEncoderMixin(ModuleSurface):
         c.y1, c.st1, c.xbm = mk((M, D), f32), mk((2, M), f32), mk((M, D), bf16)
         c.pre, c.h, c.y2, c.st2 = mk((M, I), bf16), mk((M, I), bf16), mk((M, D), f32), mk((2, M), f32)
 
+    # ---- the same saved context, as views of a RowArena (nets/surface.py): one allocation per tag, sized by the largest batch met ---------------
+    def enc_ctx_spec(self):
+        """(name, blocks, unit, elements per token row or sequence, dtype) of everything ``enc_alloc_ctx`` and ``head_alloc_ctx`` allocate."""
+        cfg = self.cfg
+        D, I, H, n = cfg.hidden, cfg.inter, cfg.heads, cfg.layers
+        f32, bf16 = torch.float32, torch.bfloat16
+        return [("xb", n + 1, "row", D, bf16), ("qkv", n, "row", 3 * D, bf16), ("ao", n, "row", D, bf16), ("lse", n, "row", H, f32),
+                ("y1", n, "row", D, f32), ("st1", n, "row", 2, f32), ("xbm", n, "row", D, bf16), ("pre", n, "row", I, bf16),
+                ("h", n, "row", I, bf16), ("y2", n, "row", D, f32), ("st2", n, "row", 2, f32),
+                ("feat", 1, "seq", D, f32), ("hpre", 1, "seq", D, f32), ("hact", 1, "seq", D, f32)]
+
+    def enc_view_ctx(self, c, arena, B, L):
+        """Fills ``c`` like enc_alloc_ctx + head_alloc_ctx do, with views of the first B * L rows (B sequences) of ``arena``'s blocks: lse is
+        [B, H, L] over a flat block, the (2, M) statistics are two row views of one."""
+        cfg = self.cfg
+        D, I, H, M, n = cfg.hidden, cfg.inter, cfg.heads, B * L, cfg.layers
+        shape = dict(xb=(M, D), qkv=(M, 3 * D), ao=(M, D), lse=(B, H, L), y1=(M, D), st1=(2, M), xbm=(M, D), pre=(M, I), h=(M, I), y2=(M, D),
+                     st2=(2, M))
+        for name, s in shape.items():
+            setattr(c, name, [arena.view(name, i, s) for i in range(n + 1 if name == "xb" else n)])
+        c.feat, c.hpre, c.hact = (arena.view(k, 0, (B, D)) for k in ("feat", "hpre", "hact"))
+
     def enc_forward(self, x, xb, ctx, save, B, L, key_len, dr, skip=None, tag="i"):
         """x fp32 [M, D] (updated in place), xb bf16 [M, D] = the same values (first layer's GEMM operand; ctx.xb[0] when save).
         dr(site, p) -> ops.Drop or None.  Returns the bf16 copy of the final x."""
@@ -68,9 +90,9 @@ class PostLNEncoderMixin(ModuleSurface):
         M = B * L
         bf16 = torch.bfloat16
         if not save:
-            qkv, ao = self._buf(tag + "qkv", (M, 3 * D), bf16), self._buf(tag + "ao", (M, D), bf16)
-            hbuf = self._buf(tag + "h", (M, I), bf16)
-            st = [self._buf(tag + "lnst%d" % j, (2, M), torch.float32) for j in range(2)]
+            qkv, ao = self._buf_rows(tag + "qkv", (M, 3 * D), bf16, M), self._buf_rows(tag + "ao", (M, D), bf16, M)
+            hbuf = self._buf_rows(tag + "h", (M, I), bf16, M)
+            st = [self._buf_rows(tag + "lnst%d" % j, (2, M), torch.float32, M) for j in range(2)]
         scale = 64 ** -0.5
         # Rows without a backward never materialise the fp32 output of a LayerNorm between two sub-layers: postln_fwd writes the bf16 GEMM operand
         # and the row statistics (6 instead of 10 bytes per element of a launch that is 11 % of the BERT leg's kernel time), `x` keeps the
@@ -124,35 +146,63 @@ class PostLNEncoderMixin(ModuleSurface):
                 pend = None
         return xb
 
+    def enc_bwd_arena(self, M, ctx):
+        """The plan of ``ctx``'s source (see enc_bwd_plan) with room for M token rows in its arena of output-gradient buffers; allocation only,
+        nothing is launched or uploaded."""
+        src = getattr(ctx, "arena", None)
+        key = ("encbwd", id(src if src is not None else ctx))
+        plan = self._buf_cache.get(key)
+        if plan is None:
+            D, I, n, bf16 = self.cfg.hidden, self.cfg.inter, self.cfg.layers, torch.bfloat16
+            plan = self._buf_cache[key] = dict(by_M={}, stager=None, src=src if src is not None else ctx)
+            plan["arena"] = self._arena(key, [("g2", n, "row", D, bf16), ("dpre", n, "row", I, bf16), ("g1", n, "row", D, bf16),
+                                              ("dqkv", n, "row", 3 * D, bf16), ("dao", 1, "row", D, bf16)], M, 0)
+            plan["arena"].on_release.append(plan["by_M"].clear)
+            if src is not None:
+                src.on_release.append(plan["by_M"].clear)
+        plan["arena"].reserve(max(M, self._reserved[0]), 0)
+        return plan
+
     def enc_bwd_plan(self, M, ctx):
         """Output-gradient buffers (bf16 A operands of dW = dY^T X), ONE SET PER LAYER, + the problem list of every layer for the weight-gradient
         launch (row-major operands, bias gradients summed on the way).  The four dY of a layer used to be shared by all layers, which forced one
         weight-gradient launch per layer inside the chain -- 108 tiles of 256 x 256 on 256 CUs (BERT: 336 us per layer, 13 % of the step).  Kept
         per layer (BERT: 113 MB x 12 of 288 GB) they feed ONE launch behind the layer loop: 1 296 tiles in a persistent walk
-        (srhip_gemm_tn_grouped_pp_f32: 113 us per layer, tools/gemm_tn_pp_bench.py)."""
-        key = ("encbwd", M, id(ctx))
-        if key in self._buf_cache:
-            return self._buf_cache[key]
+        (srhip_gemm_tn_grouped_pp_f32: 113 us per layer, tools/gemm_tn_pp_bench.py).
+
+        The buffers are views of ONE RowArena per context source (nets/surface.py): the arena of ``ctx`` when it is a view set of one (the token
+        engine: batches of many padded lengths), else ``ctx`` itself (Wav2Vec2 / HuBERT: one pad length per tag).  The arena holds the rows of the
+        largest M met; a call at M takes the leading M rows.  What depends on M -- the views, the problem list, the descriptor tables, which
+        hold the pointers of both arenas -- is kept per M inside the plan and dropped whenever either arena is replaced; the LayerNorm partials,
+        their reduce table and the TableStager do not depend on M and are made once per plan."""
+        plan = self.enc_bwd_arena(M, ctx)
         cfg = self.cfg
-        D, I = cfg.hidden, cfg.inter
-        mk = lambda c: [torch.empty(M, c, dtype=torch.bfloat16, device=self.device) for _ in range(cfg.layers)]   # noqa: E731
-        T = dict(g2=mk(D), dpre=mk(I), g1=mk(D), dqkv=mk(3 * D), dao=torch.empty(M, D, dtype=torch.bfloat16, device=self.device),
-                 probs=[], tables={})
-        G = lambda n: self.view(n, self.grad)   # noqa: E731
-        for i in range(cfg.layers):
+        D, I, n = cfg.hidden, cfg.inter, cfg.layers
+        G = lambda n_: self.view(n_, self.grad)   # noqa: E731
+        if "ln_desc" not in plan:
+            # LayerNorm affine gradients go through LN_REP partial copies per LayerNorm (ops.postln_bwd_part), folded after the layer loop
+            plan["ln_part"] = torch.zeros(2 * n, LN_REP, 2, D, dtype=torch.float32, device=self.device)
+            plan["ln_desc"] = ops.make_ln_reduce_desc([(G(self.enc_names(i)[k + "_w"]), G(self.enc_names(i)[k + "_b"]))
+                                                       for i in range(n) for k in ("ln1", "ln2")], self.device)
+        A = plan["arena"]
+        T = plan["by_M"].get(M)
+        if T is not None:
+            return T
+        if len(plan["by_M"]) >= 64:               # a run over hundreds of lengths: the oldest tables go (a few KB each, rebuilt on return)
+            plan["by_M"].pop(next(iter(plan["by_M"])))
+        mk = lambda name, c: [A.view(name, i, (M, c)) for i in range(n)]   # noqa: E731
+        T = dict(g2=mk("g2", D), dpre=mk("dpre", I), g1=mk("g1", D), dqkv=mk("dqkv", 3 * D), dao=A.view("dao", 0, (M, D)), probs=[], tables={},
+                 plan=plan, ln_part=plan["ln_part"], ln_desc=plan["ln_desc"])
+        for i in range(n):
             nm = self.enc_names(i)
             gw, gb = self.packed_qkv(i, self.grad)
             T["probs"].append([(T["g2"][i], ctx.h[i], G(nm["w2"]), G(nm["b2"]), D, I, M), (T["dpre"][i], ctx.xbm[i], G(nm["w1"]), G(nm["b1"]), I, D, M),
                                (T["g1"][i], ctx.ao[i], G(nm["o_w"]), G(nm["o_b"]), D, D, M), (T["dqkv"][i], ctx.xb[i], gw, gb, 3 * D, D, M)])
-        # LayerNorm affine gradients go through LN_REP partial copies per LayerNorm (ops.postln_bwd_part), folded after the layer loop
-        T["ln_part"] = torch.zeros(2 * cfg.layers, LN_REP, 2, D, dtype=torch.float32, device=self.device)
-        T["ln_desc"] = ops.make_ln_reduce_desc([(G(self.enc_names(i)[k + "_w"]), G(self.enc_names(i)[k + "_b"]))
-                                                for i in range(cfg.layers) for k in ("ln1", "ln2")], self.device)
-        self._buf_cache[key] = T
+        plan["by_M"][M] = T
         return T
 
     def enc_dw_table(self, T, skip):
-        """Descriptor table of the weight-gradient launch over the layers LayerDrop left in (one table per pattern, built when it first occurs)."""
+        """Descriptor table of the weight-gradient launch over the layers LayerDrop left in (one table per (M, pattern), built when it first occurs)."""
         pat = tuple(bool(s) for s in skip) if skip is not None else ()
         if pat not in T["tables"]:
             probs = [pr for i, lp in enumerate(T["probs"]) if not (pat and pat[i]) for pr in lp]
@@ -160,9 +210,10 @@ class PostLNEncoderMixin(ModuleSurface):
             # A table is built INSIDE a step whenever LayerDrop leaves out a set of layers not seen before (most of the first steps of a run): its
             # upload must not stall the host (ops.TableStager), and it allocates nothing -- the token slices that balance the persistent
             # kernel's last round meet through atomics here (slabs would be a 50-MB allocation per pattern; measured equal, 29.57 vs 29.64 ms)
-            if T.get("stager") is None:
-                T["stager"] = ops.TableStager(64 * (4 * len(T["probs"]) + 64))
-            T["tables"][pat] = (ops.make_group_tn_desc(probs, self.device, tile=256 if pp else 128, stager=T["stager"]), pp) if probs else None
+            plan = T["plan"]
+            if plan["stager"] is None:
+                plan["stager"] = ops.TableStager(64 * (4 * len(T["probs"]) + 64))
+            T["tables"][pat] = (ops.make_group_tn_desc(probs, self.device, tile=256 if pp else 128, stager=plan["stager"]), pp) if probs else None
         return T["tables"][pat]
 
     def enc_backward(self, dx, ctx, B, L, key_len, dr, skip=None):
@@ -171,7 +222,7 @@ class PostLNEncoderMixin(ModuleSurface):
         D, I, H = cfg.hidden, cfg.inter, cfg.heads
         M = B * L
         G = lambda n: self.p(n, self.grad)   # noqa: E731
-        delta = self._buf("b_delta", (B, H, L), torch.float32)
+        delta = self._buf_rows("b_delta", (B, H, L), torch.float32, M)
         T = self.enc_bwd_plan(M, ctx)
         scale = 64 ** -0.5
         for i in reversed(range(cfg.layers)):

@@ -8,6 +8,84 @@ import torch
 from .. import ops
 
 
+class RowArena:
+    """One grow-only device allocation cut into blocks whose sizes follow two capacities: token rows (B * L) and sequences (B).  The token
+    engines take their saved activations and output-gradient buffers from one: a call at (B, L) gets views of the first B * L rows of every
+    block, so a run over batches of many padded lengths holds the memory of its largest batch, not one buffer set per length.
+
+    ``spec``: [(name, count, unit, width, dtype)] -- ``count`` blocks called ``name``, each ``capacity[unit] * width`` elements (unit "row" or
+    "seq").  Every block starts at a multiple of 256 bytes of an allocation that is itself that aligned, the alignment a fresh ``torch.empty``
+    gives, so a launcher's 16-byte paths are the ones it takes on separate buffers; a block of 1 MiB or more starts at a multiple of 2 MiB, where
+    the allocator puts a large tensor of its own (packed at 256 bytes the BERT-base bench step ran 0.5 % slower than on separate buffers, at
+    2 MiB within 0.1 %: profiles/token_buckets.txt).  ``reserve`` only grows: when a call needs more rows or
+    sequences the ``on_release`` hooks run (whoever keeps views or pointers into the arena drops them), the old allocation is released, and
+    then one of the new maxima is made -- the two never coexist.  Contents never outlive a step, so nothing is copied.  Works on any
+    device (the bookkeeping is tested with CPU tensors)."""
+    ALIGN = 256
+    BIG, BIG_ALIGN = 1 << 20, 2 << 20   # a block of 1 MiB or more starts at a multiple of 2 MiB, where the allocator puts a large tensor of its own
+
+    def __init__(self, device, spec, on_alloc=None, alloc=None):
+        self.device, self.spec = torch.device(device), [tuple(s) for s in spec]
+        assert all(u in ("row", "seq") and c > 0 and w > 0 for _, c, u, w, _ in self.spec) and len({s[0] for s in self.spec}) == len(self.spec)
+        self.rows = self.seqs = self.nbytes = 0
+        self.store, self.offsets = None, {}
+        self.allocations = 0            # how often the arena was (re)made
+        self.on_release = []            # callables run before the allocation is released
+        self._on_alloc = on_alloc
+        self._alloc = alloc if alloc is not None else self._aligned_empty
+        self._dtype = {n: dt for n, _, _, _, dt in self.spec}
+        self._unit = {n: (u, w) for n, _, u, w, _ in self.spec}
+        self._esize = {n: torch.empty(0, dtype=dt).element_size() for n, _, _, _, dt in self.spec}
+
+    def _aligned_empty(self, n):
+        al = self.BIG_ALIGN if n >= self.BIG else self.ALIGN
+        raw = torch.empty(n + al, dtype=torch.uint8, device=self.device)    # (the device allocator's large blocks are aligned already: skip = 0)
+        skip = -raw.data_ptr() % al
+        return raw[skip:skip + n]
+
+    def layout(self, rows, seqs):
+        """({name: [byte offset of block 0, 1, ...]}, total bytes) at these capacities."""
+        cap, off, o = dict(row=int(rows), seq=int(seqs)), {}, 0
+        for name, count, unit, width, dt in self.spec:
+            nb = cap[unit] * width * self._esize[name]
+            al = self.BIG_ALIGN if nb >= self.BIG else self.ALIGN
+            nb, o = (nb + al - 1) // al * al, (o + al - 1) // al * al
+            off[name] = [o + i * nb for i in range(count)]
+            o += count * nb
+        return off, o
+
+    def reserve(self, rows, seqs):
+        """Makes room for ``rows`` token rows and ``seqs`` sequences.  True when the arena was replaced (every earlier view is void)."""
+        if rows <= self.rows and seqs <= self.seqs and self.store is not None:
+            return False
+        rows, seqs = max(int(rows), self.rows), max(int(seqs), self.seqs)
+        for hook in self.on_release:
+            hook()
+        self.store = None               # released BEFORE the larger one is made
+        self.offsets, self.nbytes = self.layout(rows, seqs)
+        store = self._alloc(max(self.nbytes, self.ALIGN))
+        assert store.dtype == torch.uint8 and store.data_ptr() % self.ALIGN == 0
+        self.store, self.rows, self.seqs = store, rows, seqs
+        self.allocations += 1
+        if self._on_alloc is not None:
+            self._on_alloc(self)
+        return True
+
+    def view(self, name, i, shape):
+        """The leading ``shape`` elements of block ``i`` of ``name`` (they must fit the block's capacity)."""
+        unit, width = self._unit[name]
+        dt = self._dtype[name]
+        n = int(torch.Size(shape).numel())
+        assert n <= (self.rows if unit == "row" else self.seqs) * width, (name, shape, self.rows, self.seqs)
+        o = self.offsets[name][i]
+        return self.store[o:o + n * self._esize[name]].view(dt).view(shape)
+
+    def release(self):
+        for hook in self.on_release:
+            hook()
+        self.store, self.offsets, self.rows, self.seqs, self.nbytes = None, {}, 0, 0, 0
+
+
 class ModuleSurface:
     """Base of every engine backbone: the flat parameter block (fp32 parameters, their gradient twin and, for the GEMM backbones, a bf16
     operand copy), its accessors and mode switches, the workspace cache, the refresh of the derived operand copies, and the capabilities the
@@ -41,6 +119,9 @@ class ModuleSurface:
         self.buffers = {}           # non-parameter state_dict entries (BatchNorm running statistics), after the parameters
         self.training = True
         self._buf_cache, self._pviews = {}, {}
+        self._arenas = {}                # RowArena per key (token engines: saved context per tag, output-gradient buffers per context)
+        self.arena_allocations = 0       # how often any of them was (re)made: constant once a run has met (or reserved) its largest batch
+        self._reserved = (0, 0)          # token rows, sequences every arena and rows-capacity workspace starts from (reserve_tokens)
         self._wT_desc, self._wT_stale = None, False
 
     # ---- parameter plumbing ---------------------------------------------------------------------------------------------------------
@@ -102,6 +183,34 @@ class ModuleSurface:
             t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
             self._buf_cache[key] = t
         return t
+
+    def _buf_rows(self, key, shape, dtype, rows):
+        """Rows-capacity variant of ``_buf`` for workspaces whose size follows the token rows of the call (``shape`` holds ``rows`` rows): the
+        largest allocation seen under ``key`` is kept -- at least the reserved rows (reserve_tokens) -- and the leading ``shape`` elements are
+        returned, so batches of many padded lengths share one buffer.  A fresh allocation is as aligned as ``_buf``'s."""
+        n = int(torch.Size(shape).numel())
+        ent = self._buf_cache.get(key)
+        if ent is not None and ent[1] == shape and ent[0].dtype == dtype:
+            return ent[2]
+        if ent is None or ent[0].dtype != dtype or ent[0].numel() < n:
+            self._buf_cache.pop(key, None)
+            ent = None                                                       # (released before the larger one is made)
+            flat = torch.empty(max(n, n // max(rows, 1) * self._reserved[0]), dtype=dtype, device=self.device)
+        else:
+            flat = ent[0]
+        self._buf_cache[key] = (flat, shape, flat[:n].view(shape))
+        return self._buf_cache[key][2]
+
+    def _arena(self, key, spec, rows, seqs):
+        """The RowArena ``key`` (made from ``spec`` when first asked for) with room for ``rows`` token rows and ``seqs`` sequences."""
+        a = self._arenas.get(key)
+        if a is None:
+            a = self._arenas[key] = RowArena(self.device, spec, on_alloc=self._count_arena)
+        a.reserve(max(rows, self._reserved[0]), max(seqs, self._reserved[1]))
+        return a
+
+    def _count_arena(self, arena):
+        self.arena_allocations += 1
 
     # ---- derived operand copies -----------------------------------------------------------------------------------------------------
     def refresh_operands(self):

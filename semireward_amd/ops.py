@@ -1430,6 +1430,18 @@ def embed_ln_bwd(dy, ids, seq_index, word, pos, type0, mean, rstd, gamma, dword,
           _p(dword), _p(dpos), _p(dtype0), _p(dgamma), _p(dbeta), B, L, D, pad_id, *_d(drop), _s())
 
 
+def embed_ln_bwd_ws_floats(B, L, D):
+    return int(_lib.lib().srhip_embed_ln_bwd_ws_floats(B, L, D))
+
+
+def embed_ln_bwd_ordered(dy, ids, seq_index, word, pos, type0, mean, rstd, gamma, dword, dpos, dtype0, dgamma, dbeta, ws, B, L, D, pad_id, drop=None):
+    """embed_ln_bwd with one summation order, no atomics (srhip.h): ``ws`` fp32 scratch of at least embed_ln_bwd_ws_floats(B, L, D) elements."""
+    if _CHECK_ARGS:
+        assert ws.dtype == torch.float32 and ws.numel() >= embed_ln_bwd_ws_floats(B, L, D)
+    _call("srhip_embed_ln_bwd_ordered", _p(dy), _p(ids), ids.stride(0), _p(seq_index), _p(word), _p(pos), _p(type0), _p(mean), _p(rstd), _p(gamma),
+          _p(dword), _p(dpos), _p(dtype0), _p(dgamma), _p(dbeta), _p(ws), B, L, D, pad_id, *_d(drop), _s())
+
+
 def postln_fwd(y, gamma, beta, eps, x, xb, mean, rstd, M, D):
     _call("srhip_postln_fwd", _p(y), _p(gamma), _p(beta), eps, _p(x), _p(xb), _p(mean), _p(rstd), M, D, _s())
 
@@ -1746,6 +1758,60 @@ def token_view(store, row_off, row_len, src_row, L, pad_id=0, host=None):
     _call("srhip_token_view", _p(store), _p(row_off), _p(row_len), int(row_len.shape[0]), _p(src_row), B, L, int(pad_id), _p(ids), L, _p(key_len),
           _s())
     return ids, key_len
+
+
+TOKEN_CAT_MAX_SRC = 4                                                       # srhip_token_cat: the sources ride in the kernel's arguments
+
+
+def token_len_bucket(L, bucket, cap):
+    """The padded length ``token_len_bucket: bucket`` gives a batch of padded length L: the next multiple of ``bucket``, at most ``cap``
+    (the model's positions); ``bucket`` None or 0: L."""
+    L = int(L)
+    return L if not bucket else max(L, min((L + bucket - 1) // bucket * bucket, int(cap)))
+
+
+def token_cat(sources, L_out, pad_id=0, out=None):
+    """One token batch out of up to four (srhip.h: srhip_token_cat), one launch: ``sources`` = [(ids int64 [S, L] contiguous, key_len int32
+    [S], seq_len int32 [S] or None), ...] on one device -> (ids int64 [sum S, L_out], key_len int32 [sum S], seq_len int32 [sum S]); a row is
+    its source row filled up with ``pad_id``, seq_len the source's own or its L.  ``out``: the three outputs (contiguous, of exactly these
+    shapes) -- nothing is allocated then.  Refused here, before anything is launched: no or more than four sources, an L_out below a
+    source's L, ids that are not contiguous, wrong dtypes or shapes."""
+    sources, L_out = list(sources), int(L_out)
+    if not 1 <= len(sources) <= TOKEN_CAT_MAX_SRC:
+        raise ValueError("token_cat: takes 1 .. %d sources, got %d" % (TOKEN_CAT_MAX_SRC, len(sources)))
+    if int(pad_id) < 0:
+        raise ValueError("token_cat: pad_id is a token id, got %d" % pad_id)
+    dev, total = sources[0][0].device, 0
+    for j, (ids, kl, sl) in enumerate(sources):
+        if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] < 1 or ids.shape[1] < 1:
+            raise ValueError("token_cat: ids of source %d is int64 [S, L], got %s %s" % (j, ids.dtype, tuple(ids.shape)))
+        if not ids.is_contiguous():
+            raise ValueError("token_cat: ids of source %d is not contiguous (strides %s)" % (j, tuple(ids.stride())))
+        S, L = ids.shape
+        if L > L_out:
+            raise ValueError("token_cat: L_out = %d is below the L = %d of source %d" % (L_out, L, j))
+        for n, t in (("key_len", kl), ("seq_len", sl)):
+            if t is None and n == "seq_len":
+                continue
+            if t is None or t.dtype != torch.int32 or tuple(t.shape) != (S,) or not t.is_contiguous():
+                raise ValueError("token_cat: %s of source %d is int32 [%d] contiguous, got %s" % (
+                    n, j, S, None if t is None else "%s %s" % (t.dtype, tuple(t.shape))))
+        if any(t is not None and t.device != dev for t in (ids, kl, sl)):
+            raise ValueError("token_cat: every source lives on one device, source %d does not (%s)" % (j, dev))
+        total += S
+    if total > 65535:
+        raise ValueError("token_cat: %d rows, more than the 65535 of one launch" % total)
+    if out is None:
+        out = (torch.empty(total, L_out, dtype=torch.int64, device=dev), torch.empty(total, dtype=torch.int32, device=dev),
+               torch.empty(total, dtype=torch.int32, device=dev))
+    o_ids, o_kl, o_sl = out
+    if (o_ids.dtype != torch.int64 or tuple(o_ids.shape) != (total, L_out) or not o_ids.is_contiguous()
+            or any(t.dtype != torch.int32 or tuple(t.shape) != (total,) or not t.is_contiguous() for t in (o_kl, o_sl))
+            or any(t.device != dev for t in out)):
+        raise ValueError("token_cat: out is (int64 [%d, %d], int32 [%d], int32 [%d]), contiguous, on %s" % (total, L_out, total, total, dev))
+    arr = (_lib.TokenSrc * len(sources))(*[_lib.TokenSrc(_p(ids), _p(kl), _p(sl), ids.shape[0], ids.shape[1]) for ids, kl, sl in sources])
+    _call("srhip_token_cat", ctypes.addressof(arr), len(sources), int(pad_id), _p(o_ids), L_out, _p(o_kl), _p(o_sl), _s())
+    return o_ids, o_kl, o_sl
 
 
 TOKEN_COPY, TOKEN_DELETE, TOKEN_MASK, TOKEN_CUTOFF, TOKEN_SWAP = range(5)   # srhip_token_strong ops (srhip.h: SR_TOKEN_*)

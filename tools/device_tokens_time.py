@@ -10,8 +10,7 @@
     without its per-step tokenisation, main process; skipped with a note when transformers is not importable), and ``TokenBatch.from_dict`` of
     the padded host tensors (the copy to the device + the cast + srhip_mask_lengths), host time per step and, with events, device-side time.
 
-Row lengths are a handful of values (128, 256, 384, 512): the BERT engine keeps one workspace per distinct (B, L).  Nothing here is a pass /
-fail number.
+Row lengths are a handful of values (128, 256, 384, 512).  Nothing here is a pass / fail number.
 
     python tools/device_tokens_time.py > profiles/device_tokens.txt
 """

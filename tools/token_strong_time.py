@@ -8,9 +8,10 @@
       around ``next()`` of both loaders without a device synchronise, and the first step of an epoch (the draws, the table, its one copy);
   (c) the SRSoftMatch step on the tiny BERT and on BERT-base fed by the key's loader against a ``data_s`` loader over the same sentences: ONE
       algorithm object, interleaved rounds, wall ms per step with a synchronise at the end of a round, medians and the spread between the
-      rounds of one setting.  The rounds replay an epoch that was run once before (the loaders replay their draws), so every (B, L) workspace
-      of the BERT engine exists: the key's strong view meets more padded lengths than ``data_s`` (the engine keeps one workspace set per
-      distinct (B, L)), and the first pass, which allocates them, is reported on its own line;
+      rounds of one setting.  The rounds replay an epoch that was run once before (the loaders replay their draws), so every shape has met
+      the BERT engine: the key's strong view meets more padded lengths than ``data_s`` (when profiles/token_strong.txt was taken the
+      engine kept one workspace set per distinct (B, L); its arenas are sized by the largest batch now), and the first pass is reported on
+      its own line;
   (d) ``--bench-lines FILE``: lines "this {json}" / "parent {json}" of alternating ``bench.py --gpus 1`` runs of this tree and of the parent
       commit's tree on the same box -> the ratio of medians beside the parent's own run-to-run spread.
 
