@@ -48,6 +48,8 @@ from semireward_amd import ops
 C_ACC_MEASURED, DGELU_ABS_MEASURED = 2.887, 2.676e-7
 C_ACC, DGELU_ABS = 8.0 * C_ACC_MEASURED, 8.0 * DGELU_ABS_MEASURED
 GELU_L, GELU_E = 1.13, 1e-6
+# what test_gelu_forms_against_exact_erf holds gelu_poly2 (the GELU inside srhip_mlp_fused_proj) to: |gelu_poly2(x) - GELU(x)| <= max(ABS, REL |x|)
+GELU_POLY2_ABS, GELU_POLY2_REL = 7e-5, 5e-6
 
 FRONT, ROWS_AFTER = 64, 64          # elements before the first, rows after the last (operands and outputs)
 PATTERN = 0x4B1D                    # every 16 bits of the output padding: 9.96e6 as bf16, 1.03e7 as fp32 (0x4B1D4B1D), finite in both
